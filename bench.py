@@ -21,6 +21,15 @@ of R partial chains).
 C5 (--config c5) is feature-sharded: d/N columns per rank, no collective. The barrier and the
 max-over-ranks time go over RCCL.
 
+A plain run sets up, warms up, times --steps steps, writes --dump-outputs if asked, and prints the
+JSON line (rank 0). --full adds what takes runs of its own: cpu_baseline (one GPU), the collectives
+probe and the chosen grid's projection (N GPUs), the harness timings (--workload train, one GPU).
+
+--dump-outputs DIR: after the timed steps, what the last timed step returned to its caller (the
+propagated table; for --workload train the embedding tables after the last step) as DIR/<name>.npy,
+float32, at most 64 MB in all (a larger output: a fixed, seeded sample of its rows). The inputs are
+seeded, so two builds run with the same arguments can be compared output for output.
+
 Also reported (one JSON line on rank 0):
   roofline     — the dominant kernel (the item pass, k_spmm_vec; at C2 one launch per source
                  slice, lgcn_amd.sliced), its launch time measured live with HIP events on its
@@ -30,7 +39,7 @@ Also reported (one JSON line on rank 0):
                  of the schedule stand in (basis "compulsory", a lower bound). Also: the schedule's
                  compulsory bytes, SURVEY §8d's no-reuse algorithmic bytes as effective_GBps.
   cpu_baseline — the reference's CPU op sequence (PyG 2.4.0 LGConv restated with torch CPU
-                 primitives, oracle/lgconv_torch.py) on the whole C2 graph, rank 0, N=1 only.
+                 primitives, oracle/lgconv_torch.py) on the whole C2 graph, rank 0, N=1, --full only.
 """
 from __future__ import annotations
 
@@ -51,6 +60,37 @@ GATHER_L2_PEAK_GBS = 18800.0  # fully L2-resident row gathers, chip-wide (MI355X
 
 def log(*a):
     print(*a, file=sys.stderr, flush=True)
+
+
+DUMP_MAX_BYTES = 64 * 10**6  # --dump-outputs: all files together
+
+
+def dump_outputs(directory, arrays: dict) -> dict:
+    """--dump-outputs: each array of `arrays` (name -> tensor, 2-D, the timed path's last result)
+    as directory/<name>.npy in float32. Within DUMP_MAX_BYTES in all the arrays are written whole;
+    beyond it every array keeps the same share of its rows, picked by a generator seeded with 0
+    (sorted, so the same rows from run to run and from build to build). Returns what was written:
+    name -> {shape, rows_of, sampled}."""
+    import numpy as np
+    import torch
+
+    out = pathlib.Path(directory)
+    out.mkdir(parents=True, exist_ok=True)
+    total = sum(int(t.numel()) * 4 for t in arrays.values())
+    share = min(1.0, DUMP_MAX_BYTES / max(1, total))
+    rng = np.random.default_rng(0)
+    written = {}
+    for name, t in arrays.items():
+        t = t.detach()
+        rows = int(t.shape[0])
+        if share < 1.0:
+            keep = max(1, int(rows * share))
+            idx = np.sort(rng.choice(rows, size=keep, replace=False))
+            t = t[torch.from_numpy(idx).to(t.device)]
+        a = np.ascontiguousarray(t.to(torch.float32).cpu().numpy())
+        np.save(out / f"{name}.npy", a)
+        written[name] = {"shape": list(a.shape), "rows_of": rows, "sampled": share < 1.0}
+    return written
 
 
 TIMER_EVERY = 5
@@ -643,7 +683,14 @@ def main():
     ap.add_argument("--dim", type=int, default=None, help="d (default 64 for c2, 256 for c5; train: 128)")
     ap.add_argument("--scale", type=float, default=1.0, help="graph scale vs ML-25M (1.0 = C2)")
     ap.add_argument("--chunk", type=int, default=None)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the CPU baseline (one GPU), the "
+                         "collectives probe and the chosen grid's projection (N GPUs), the harness timings "
+                         "(--workload train, one GPU)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy "
+                         "(float32, at most 64 MB in all: a seeded row sample of a larger output)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: leave the CPU baseline out")
     ap.add_argument("--tune", action="append", default=[], metavar="FIELD=VALUE",
                     help="A/B: set one lgcn_amd.tuning field for the run (repeatable; the defaults are the "
                          "measured choices, and the JSON line lists any field set)")
@@ -680,7 +727,7 @@ def main():
                          "auto: the projection's pick (tools/project_c4.py, DESIGN §7): columns at N <= 2, "
                          "owner from N = 4")
     ap.add_argument("--no-harness", action="store_true",
-                    help="train, N=1: skip timing utils.train_test.train() both ways after the bench line's run")
+                    help="train, N=1, --full: skip timing utils.train_test.train() both ways after the bench line's run")
     ap.add_argument("--dense-adam", action="store_true",
                     help="train: dense FusedAdam over all rows every step instead of the row-lazy exact Adam")
     ap.add_argument("--autograd", action="store_true",
@@ -812,7 +859,8 @@ def main():
         for R, F, _ in cands:  # every rank creates every column group, in one order
             if R > 1 and (R, F) not in groups:
                 groups[(R, F)] = ShardGrid.build(world, rank, d_full, R, F).exchange_group(dist)
-        collectives = probe_collectives(dist, torch, dev, c2_collective_specs(world, d_full, I, groups, cands))
+        collectives = (probe_collectives(dist, torch, dev, c2_collective_specs(world, d_full, I, groups, cands))
+                       if args.full else [])
         for c in collectives:
             log(f"[rank {rank}] collective {c['name']}: {c['bytes'] / 1e6:.3f} MB over {c['ranks']} ranks, "
                 f"{c['ms']} ms, bus {c['busbw_GBps']} GB/s")
@@ -908,6 +956,7 @@ def main():
         if exchange is not None:
             exchange.bytes = 0
         step_ev = [] if args.step_times else None
+        last_out, last_kept = None, (args.steps - 1 if args.dump_outputs else -1)
         if distributed:
             dist.barrier()
         torch.cuda.synchronize()
@@ -917,7 +966,10 @@ def main():
             if step_ev is not None:
                 step_ev.append(torch.cuda.Event(enable_timing=True))
                 step_ev[-1].record(torch.cuda.current_stream())
-            step()
+            if i == last_kept:
+                last_out = step()  # --dump-outputs: what the last timed step returns, held past the loop
+            else:
+                step()
         host_s = time.perf_counter() - t0  # the host's own time to issue the steps (diagnostic)
         if step_ev is not None:
             step_ev.append(torch.cuda.Event(enable_timing=True))
@@ -1042,7 +1094,13 @@ def main():
         result["config"]["tuning"] = args.tuned  # the source-sliced schedule's hub chunk
     if grid_trials is not None:
         result["config"]["grid_trials_ms_per_step"] = grid_trials
-    if sharded:
+    if args.dump_outputs and rank == 0 and last_out is not None:
+        # rank 0's own result (N > 1: its share of the rows / columns, as the grid hands it back)
+        outs = last_out if isinstance(last_out, (tuple, list)) else (last_out,)
+        names = ["embeddings"] if len(outs) == 1 else ["users", "items"][:len(outs)]
+        result["dumped_outputs"] = dump_outputs(args.dump_outputs, dict(zip(names, outs)))
+    del last_out
+    if sharded and args.full:
         result["collectives"] = collectives
         result["projection"] = project_chosen_grid(st, K, collectives, elapsed / args.steps * 1e3, torch, dist)
     if step_ev is not None:
@@ -1056,7 +1114,7 @@ def main():
         else:
             result["exchange"] = {"mode": exchange.mode, "block_exchanges_per_step": 2 * (K - 1),
                                   "MB_received_per_rank_per_step": exchange.bytes / args.steps / 1e6}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         if c5:
             # C5 does not fit a CPU run: the same generator at 1/100 scale (5e6 edges), K and d of C5
             del ei, user_w, item_w
@@ -1250,7 +1308,7 @@ def run_train(args):
                                neg_seed=(7 if cols is not None else 1000 + rank) if dp_mode != "replicated" else None)
 
     collectives = None
-    if world > 1:  # what this mode exchanges, timed on the node before the warm-up (untimed)
+    if world > 1 and args.full:  # what this mode exchanges, timed on the node before the warm-up (untimed)
         max_b = max(int((b.edge_index[0] < U).sum()) for b in batches)
         collectives = probe_collectives(dist, torch, dev, c4_collective_specs(world, dp_mode, exchange, cols, I, d,
                                                                               max_b))
@@ -1351,7 +1409,12 @@ def run_train(args):
         result["exchange"] = {"mode": dp_mode, "MB_received_per_rank_per_step": exchange.bytes / args.steps / 1e6}
     if collectives is not None:
         result["collectives"] = collectives
-    if world == 1 and not args.no_harness:
+    if args.dump_outputs and rank == 0:
+        # what a caller of the step holds after it: the embedding tables (made current by the last
+        # timed step's sync; N > 1: rank 0's tables / column share)
+        result["dumped_outputs"] = dump_outputs(args.dump_outputs, {"user_embedding": model.user_embedding.weight,
+                                                                    "item_embedding": model.item_embedding.weight})
+    if world == 1 and args.full and not args.no_harness:
         # what a user of the reference harness gets: utils.train_test.train() over one epoch of the
         # same batches with the reference's torch Adam(1e-3) (clip 1 inside), routed to the fused
         # step (lgcn_amd.harness), next to the reference-style loop it replaces (untimed by the line)

@@ -10,7 +10,7 @@ Two anchors, because the reference's hot path is split across two places:
    with Adam(1e-3) + clip(1) (post-step weights), and evaluate() (loss, Recall@100).
    The model those harness functions drive is the reference's own LightGCN class (below).
 
-2. lgconv_cases.npz — forward/backward of the reference's OWN LightGCN class: reference
+2. lgconv_cases/part_*.npz — forward/backward of the reference's OWN LightGCN class: reference
    models/light_gcn.py:13-40 is loaded unmodified from /root/reference with its one missing
    import, ``torch_geometric.nn.LGConv`` (PyG 2.4.0, absent here: an ordinary
    ModuleNotFoundError, SURVEY.md §8c), supplied IN MEMORY by oracle/lgconv_torch.py::OracleLGConv
@@ -148,7 +148,9 @@ def lgconv_cases():
     run("c1_K2_d64", g.num_users, g.num_items, g.edge_index, 2, 64,
         weights=graphs.embeddings(g.num_users, g.num_items, 64, 6), seed=6)
     flat = {f"{c}__{k}": v for c, arrs in cases.items() for k, v in arrs.items()}
-    np.savez_compressed(HERE / "lgconv_cases.npz", cases=np.array(sorted(cases)), **flat)
+    from golden_io import save_parts  # several small files: tests/golden_io.py
+
+    save_parts(HERE / "lgconv_cases", dict(cases=np.array(sorted(cases)), **flat))
     print("lgconv_cases:", sorted(cases))
 
 

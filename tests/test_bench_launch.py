@@ -98,6 +98,43 @@ def test_traffic_entry_needs_a_matching_signature(tmp_path, monkeypatch):
     assert b.load_traffic(sig)[0] is None
 
 
+def test_dump_outputs_whole_and_sampled(tmp_path, monkeypatch):
+    """--dump-outputs: float32 .npy files; whole arrays within the byte bound, beyond it the same
+    seeded, sorted row sample on every call, all files together within the bound."""
+    import numpy as np
+    import torch
+
+    b = _bench()
+    g = torch.Generator().manual_seed(3)
+    users, items = torch.randn(101, 8, generator=g, dtype=torch.float64), torch.randn(37, 8, generator=g)
+    rec = b.dump_outputs(tmp_path / "whole", {"users": users, "items": items})
+    got = np.load(tmp_path / "whole" / "users.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, users.to(torch.float32).numpy())
+    assert np.array_equal(np.load(tmp_path / "whole" / "items.npy"), items.numpy())
+    assert rec["users"] == {"shape": [101, 8], "rows_of": 101, "sampled": False}
+
+    monkeypatch.setattr(b, "DUMP_MAX_BYTES", 2000)  # of 138 rows x 32 bytes = 4416
+    rec = b.dump_outputs(tmp_path / "a", {"users": users, "items": items})
+    b.dump_outputs(tmp_path / "b", {"users": users, "items": items})
+    total = 0
+    for name, src in (("users", users), ("items", items)):
+        a = np.load(tmp_path / "a" / f"{name}.npy")
+        assert np.array_equal(a, np.load(tmp_path / "b" / f"{name}.npy"))
+        assert rec[name]["sampled"] and rec[name]["rows_of"] == src.shape[0] and 1 <= a.shape[0] < src.shape[0]
+        # every kept row is a row of the source, in the source's order
+        src32 = src.to(torch.float32).numpy()
+        pos = [int(np.flatnonzero((src32 == r).all(axis=1))[0]) for r in a]
+        assert pos == sorted(set(pos))
+        total += a.nbytes
+    assert total <= 2000
+
+
+def test_full_and_dump_options_parse():
+    """bench.py knows --full and --dump-outputs DIR (the launcher hands its argv to every rank)."""
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "--full" in r.stdout and "--dump-outputs DIR" in r.stdout
+
+
 def test_committed_c2_entry_matches_its_kernel_source():
     """The committed C2 PMC entry was measured on the kernel source in the tree."""
     b = _bench()
@@ -192,7 +229,7 @@ def _collectives_worker(rank, world, port, out):
 
 
 def test_collectives_probe_schema(tmp_path):
-    """bench.py --gpus N times the collectives its projections price (untimed,
+    """bench.py --gpus N --full times the collectives its projections price (untimed,
     before the grid trials / the training warm-up) and writes them into the JSON line: name, op,
     ranks, bytes, ms (max over ranks), bus and algorithm bandwidth; a collective the backend lacks
     is recorded as failed on every rank instead of ending the run. World-2 gloo rehearsal."""

@@ -1,4 +1,4 @@
-"""Every golden case (tests/golden/lgconv_cases.npz: outputs of the reference's OWN LightGCN
+"""Every golden case (tests/golden/lgconv_cases/: outputs of the reference's OWN LightGCN
 class, reference models/light_gcn.py:13-40, with PyG 2.4.0's LGConv restated on torch CPU
 primitives; see tests/golden/make_golden.py) run through the HIP path on the GPU.
 
@@ -13,11 +13,12 @@ import pytest
 import torch
 
 from conftest import GOLDEN
+from golden_io import load_parts
 from parity import assert_rows_close
 
 pytestmark = pytest.mark.gpu
 
-_G = np.load(GOLDEN / "lgconv_cases.npz")
+_G = load_parts(GOLDEN / "lgconv_cases")
 CASES = [str(c) for c in _G["cases"]]
 
 

@@ -4,10 +4,11 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN
+from golden_io import load_parts
 from oracle import c_oracle
 from oracle import lgconv_ref as R
 
-_G = np.load(GOLDEN / "lgconv_cases.npz")
+_G = load_parts(GOLDEN / "lgconv_cases")
 CASES = [str(c) for c in _G["cases"]]
 
 

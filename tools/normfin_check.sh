@@ -11,7 +11,7 @@ timeout -k 10 600 python -u -m pytest tests/test_gpu_program.py tests/test_gpu_t
   tests/test_gpu_scatter.py -x -v --timeout 300 --timeout-method thread > "$O/tests.log" 2>&1 || exit $?
 for i in 1 2; do
   for cap in 32768 0; do
-    timeout -k 10 300 python -u bench.py --workload train --steps 300 --warmup 30 --no-cpu-baseline \
+    timeout -k 10 300 python -u bench.py --workload train --steps 300 --warmup 30 --full --no-cpu-baseline \
       --tune norm_in_update_max_rows=$cap $([ $cap = 0 ] && echo --no-harness) > "$O/c3_cap${cap}_$i.log" 2>&1 || exit $?
   done
 done

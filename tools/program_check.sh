@@ -10,7 +10,7 @@ timeout -k 10 600 python -u -m pytest tests/test_gpu_program.py tests/test_gpu_t
   -x -v --timeout 300 --timeout-method thread > "$O/tests.log" 2>&1 || exit $?
 for g in ml25m planted; do
   for i in 1 2; do
-    timeout -k 10 300 python -u bench.py --workload train --graph $g --steps 200 --warmup 20 --no-cpu-baseline \
+    timeout -k 10 300 python -u bench.py --workload train --graph $g --steps 200 --warmup 20 --full --no-cpu-baseline \
       --tune step_program=1 $([ $g = planted ] && echo --no-harness) > "$O/${g}_program_$i.log" 2>&1 || exit $?
     timeout -k 10 300 python -u bench.py --workload train --graph $g --steps 200 --warmup 20 --no-cpu-baseline \
       --no-harness --tune step_program=0 > "$O/${g}_graph_$i.log" 2>&1 || exit $?

@@ -11,5 +11,5 @@ P=29540
 for spec in 2x2:allgather 2x2:reduce 2x2:reduce-fused 2x2:reduce-a2a 2x2:reduce-a2a-fused 4x1:p2p; do
   g=${spec%%:*}; m=${spec##*:}; P=$((P + 1))
   timeout -k 10 240 $R --master-port $P bench.py --gpus 4 --steps 5 --warmup 2 --dist-backend gloo \
-    --shard $g --exchange-mode $m --no-cpu-baseline > $O/c2_n4_${g}_${m}.log 2>&1 || exit 1
+    --shard $g --exchange-mode $m --full --no-cpu-baseline > $O/c2_n4_${g}_${m}.log 2>&1 || exit 1
 done

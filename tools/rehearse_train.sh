@@ -6,7 +6,7 @@ set -o pipefail
 cd $GRAFT_REPO_ROOT
 O=gpurun_out/${1:-rehearse_train}; mkdir -p $O
 R="python -m torch.distributed.run --nnodes=1 --master-addr 127.0.0.1"
-timeout -k 10 300 python -u bench.py --workload train > $O/c3_w1.log 2>&1 && \
-timeout -k 10 300 python -u bench.py --workload train --exchange > $O/c3_w1_exchange.log 2>&1 && \
-timeout -k 10 300 $R --nproc-per-node 2 --master-port 29521 bench.py --workload train --gpus 2 --steps 20 --warmup 4 --dist-backend gloo > $O/c4_n2_gloo.log 2>&1 && \
-timeout -k 10 400 $R --nproc-per-node 4 --master-port 29522 bench.py --workload train --gpus 4 --steps 20 --warmup 4 --dist-backend gloo > $O/c4_n4_gloo.log 2>&1
+timeout -k 10 300 python -u bench.py --workload train --full > $O/c3_w1.log 2>&1 && \
+timeout -k 10 300 python -u bench.py --workload train --exchange --full > $O/c3_w1_exchange.log 2>&1 && \
+timeout -k 10 300 $R --nproc-per-node 2 --master-port 29521 bench.py --workload train --gpus 2 --steps 20 --warmup 4 --dist-backend gloo --full > $O/c4_n2_gloo.log 2>&1 && \
+timeout -k 10 400 $R --nproc-per-node 4 --master-port 29522 bench.py --workload train --gpus 4 --steps 20 --warmup 4 --dist-backend gloo --full > $O/c4_n4_gloo.log 2>&1
