@@ -623,6 +623,33 @@ int lgcn_select_topk(const uint32_t* list_key, const int32_t* list_idx, const in
 int lgcn_select_topk_stl(uint32_t* list_key, int32_t* list_idx, int64_t cap, int64_t M, int32_t k, int64_t P,
                          int64_t Qpad, int64_t Qvalid, int32_t* hits_out, lgcn_stream_t stream);
 
+/* Ranked top-k with seen-item exclusion (added under ABI 11, purely additive; the product of
+ * reference utils/recommend.py: which candidates, in which order). Reads the per-query (key, index)
+ * lists lgcn_score_filter writes — dense rows (list_n NULL, dense_n entries) or filtered lists
+ * (list_n[q] entries, a count above cap meaning "clamped to cap") — one workgroup per query.
+ *   exclusion: CSR (excl_ptr int64[excl_rows + 1], excl_idx int32 candidate indices ascending
+ *     within a row); query q drops every list entry whose index is in row excl_row[q] (row q when
+ *     excl_row is NULL; a row outside [0, excl_rows) drops nothing). excl_ptr NULL: no exclusion.
+ *   ranking rule: the remaining (eligible) entries by key descending, then candidate index
+ *     ascending — total and deterministic, whatever order the filter appended equal scores in.
+ *     NaN scores carry the highest key and rank first, as torch.sort(descending=True) has them.
+ *   threshold mode (thr_out set): thr_out[q] = key of the k-th best eligible entry, 0 ("accept
+ *     everything") when fewer than k are eligible; a threshold formed on a candidate subset is a
+ *     lower bound of the k-th best eligible score of all candidates.
+ *   emit mode (out_idx, out_score and out_n set, each [Qpad, k] / [Qpad]): out_idx[q, 0:k] and
+ *     out_score[q, 0:k] hold the winners in rank order (the f32 score behind the key),
+ *     out_n[q] = min(k, eligible entries); slots past out_n[q] hold index -1 and score -inf.
+ *   padding queries [Qvalid, Qpad): thr_out = 0xFFFFFFFF, out_n = 0, every slot -1 / -inf.
+ * Limits: 1 <= k <= LGCN_RANKED_MAX_K (the winners are ranked in LDS), k <= cap <=
+ * LGCN_RANKED_MAX_CAP (one eligibility bit per list entry in LDS; LGCN_E_UNSUPPORTED above it).
+ * Both modes may be asked for in one call. */
+#define LGCN_RANKED_MAX_K 1024
+#define LGCN_RANKED_MAX_CAP 262144
+int lgcn_select_topk_ranked(const uint32_t* list_key, const int32_t* list_idx, const int32_t* list_n, int32_t dense_n,
+                            int32_t cap, int32_t k, int64_t Qpad, int64_t Qvalid, const int64_t* excl_ptr,
+                            const int32_t* excl_idx, const int64_t* excl_row, int64_t excl_rows, uint32_t* thr_out,
+                            int32_t* out_idx, float* out_score, int32_t* out_n, lgcn_stream_t stream);
+
 /* Host-only (no GPU): `draws` consecutive numpy legacy np.random.choice(n, size, replace=False)
  * calls (reference utils/train_test.py:187) on the MT19937 state (key[624], *pos) of
  * np.random.get_state(), written to out[draws*size]; key/pos are advanced exactly as numpy would

@@ -27,6 +27,8 @@ ITEM_BYTES = 16   # lgcn_item_t {int64 beg; int32 len; int32 dst}
 SPLIT_BYTES = 16  # lgcn_split_t {int32 row, pbeg, pcnt, pad}
 ABI_VERSION = 11  # LGCN_ABI_VERSION of include/lgcn.h this binding speaks
 DIGEST_BLOCKS = 1024  # LGCN_DIGEST_BLOCKS
+RANKED_MAX_K = 1024  # LGCN_RANKED_MAX_K
+RANKED_MAX_CAP = 262144  # LGCN_RANKED_MAX_CAP
 
 _lib = None
 
@@ -129,6 +131,8 @@ _SIGS = {
     "lgcn_select_topk": ([_vp, _vp, _vp, _i32, _i32, _i32, _i64, _i64, _i64, _vp, _vp, _vp], ctypes.c_int),
     "lgcn_digest128": ([_vp, _i64, _vp, _i64, _vp, _vp], ctypes.c_int),
     "lgcn_select_topk_stl": ([_vp, _vp, _i64, _i64, _i32, _i64, _i64, _i64, _vp, _vp], ctypes.c_int),
+    "lgcn_select_topk_ranked": ([_vp, _vp, _vp, _i32, _i32, _i32, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp,
+                                 _vp], ctypes.c_int),
     "lgcn_legacy_choice": ([_vp, _vp, _i64, _i64, _i64, _vp], ctypes.c_int),
     "lgcn_slice_schedule_workspace_size": ([_i64, _i64, _i32, _i32, _vp, _vp], ctypes.c_int),
     "lgcn_slice_schedule_build": ([_vp, _vp, _i64, _i64, _vp, _i32, _i32, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp,

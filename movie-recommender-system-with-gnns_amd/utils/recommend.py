@@ -1,0 +1,150 @@
+"""Recommendations from a trained model — the reference's utils/recommend.py API on the HIP path.
+
+``recommend_from_user(model, user_id, data_handler, excluded_train_items=None)`` and
+``recommend_from_movie(model, movie_id, data_handler, excluded_train_users=None)`` keep the
+reference's signatures, inputs (the raw rows of ``model.get_embeddings``, cosine-scored) and return
+shapes: {'recommendations': [{'title', 'score'} x 10]}, {'top_users': [{'user_id', 'score'} x 10]}
+or {'error': 'Invalid user ID' / 'Invalid movie ID'}; fewer than ten entries when fewer candidates
+are left. Where the reference sorts a dense score row and walks it in Python, one
+lgcn_amd.recommend.topk_rows call with a one-row exclusion CSR ranks on the device; equal scores
+come in ascending index order. ``recommend_for_users`` serves a batch of users in one call.
+Not carried over: the plotting (``visualizations``) and the import-time seeding (nothing here draws
+random numbers). Unknown ids are answered without touching the GPU; everything else needs the model
+on a ROCm device (lgcn_amd._ffi.LgcnError otherwise, there is no CPU fallback).
+"""
+from typing import Any, Dict, List, Optional, Sequence, Union
+
+import torch
+
+if __name__ == '__main__':  # run as a script: the package root (this file's parent's parent) is not on the path yet
+    import os
+    import sys
+
+    sys.path.insert(0, os.path.abspath(os.path.join(os.path.dirname(os.path.abspath(__file__)), '..')))
+
+from lgcn_amd import recommend as _rec
+
+TOP_N = 10  # the reference's list length
+
+
+def _one_row_csr(excluded, num_candidates: int, device):
+    """The exclusion CSR of one query from a list or tensor of candidate indices."""
+    if excluded is None:
+        return None
+    e = torch.as_tensor(excluded, dtype=torch.int64, device=device).view(-1)
+    e = torch.unique(e[(e >= 0) & (e < num_candidates)], sorted=True)
+    ptr = torch.tensor([0, e.numel()], dtype=torch.int64, device=device)
+    return ptr, e.to(torch.int32)
+
+
+def _id_map(handler, name: str, forward: Dict[int, int]) -> Dict[int, int]:
+    """index -> id (the handler's own inverse map when it keeps one)."""
+    inv = getattr(handler, name, None)
+    return inv if inv is not None else {i: k for k, i in forward.items()}
+
+
+def _title_of(movies) -> Dict[int, str]:
+    first = movies.drop_duplicates("movieId")
+    return dict(zip(first["movieId"].tolist(), first["title"].tolist()))
+
+
+def _ranked(idx: torch.Tensor, score: torch.Tensor):
+    """Host lists of one topk_rows result, the unfilled (-1) slots dropped."""
+    idx, score = idx.cpu(), score.cpu()
+    return [[(int(i), float(s)) for i, s in zip(ri.tolist(), rs.tolist()) if i >= 0] for ri, rs in zip(idx, score)]
+
+
+def recommend_from_user(model: torch.nn.Module, user_id: int, data_handler: Any,
+                        excluded_train_items: Optional[Union[List[int], torch.Tensor]] = None
+                        ) -> Dict[str, Union[str, List[Dict[str, Union[str, float]]]]]:
+    """The ten best movies for a user, without ``excluded_train_items`` (0-based item indices)."""
+    user_id_map, movie_id_map = data_handler.user_id_map, data_handler.movie_id_map
+    user_index = user_id_map.get(user_id)
+    if user_index is None:
+        return {'error': 'Invalid user ID'}
+    num_users, num_items = len(user_id_map), len(movie_id_map)
+    dev = model.user_embedding.weight.device
+    with torch.no_grad():
+        user_emb, item_emb = model.get_embeddings(user_indices=torch.tensor([user_index], device=dev),
+                                                  item_indices=torch.arange(num_items, device=dev))
+        idx, score = _rec.topk_rows(user_emb, torch.arange(1), item_emb, min(TOP_N, max(num_items, 1)),
+                                    excl=_one_row_csr(excluded_train_items, num_items, dev))
+    id_movie = _id_map(data_handler, "id_movie_map", movie_id_map)
+    movies = data_handler.movies
+    recommendations = []
+    for i, s in _ranked(idx, score)[0]:
+        movie_id = id_movie[i + num_users]
+        recommendations.append({'title': movies.loc[movies['movieId'] == movie_id, 'title'].iloc[0], 'score': s})
+    return {'recommendations': recommendations}
+
+
+def recommend_from_movie(model: torch.nn.Module, movie_id: int, data_handler: Any,
+                         excluded_train_users: Optional[Union[List[int], torch.Tensor]] = None
+                         ) -> Dict[str, Union[str, List[Dict[str, Union[int, float]]]]]:
+    """The ten best users for a movie, without ``excluded_train_users`` (user indices)."""
+    user_id_map, movie_id_map = data_handler.user_id_map, data_handler.movie_id_map
+    movie_index = movie_id_map.get(movie_id)
+    if movie_index is None:
+        return {'error': 'Invalid movie ID'}
+    num_users = len(user_id_map)
+    movie_index -= num_users
+    dev = model.user_embedding.weight.device
+    with torch.no_grad():
+        user_emb, item_emb = model.get_embeddings(user_indices=torch.arange(num_users, device=dev),
+                                                  item_indices=torch.tensor([movie_index], device=dev))
+        idx, score = _rec.topk_rows(item_emb, torch.arange(1), user_emb, min(TOP_N, max(num_users, 1)),
+                                    excl=_one_row_csr(excluded_train_users, num_users, dev))
+    id_user = _id_map(data_handler, "id_user_map", user_id_map)
+    return {'top_users': [{'user_id': id_user[i], 'score': s} for i, s in _ranked(idx, score)[0]]}
+
+
+def recommend_for_users(model: torch.nn.Module, user_ids: Sequence[int], data_handler: Any, k: int = 10,
+                        exclude_seen: bool = True, train_edge_index: Optional[torch.Tensor] = None
+                        ) -> List[Union[Dict[str, str], List[Dict[str, Union[int, str, float]]]]]:
+    """One entry per id of ``user_ids``: the user's k best movies as [{'movie_id', 'title', 'score'}],
+    or {'error': 'Invalid user ID'} for an unknown id. With ``exclude_seen`` the movies a user has an
+    edge to in ``train_edge_index`` (default: every edge the handler holds, ``data_handler.edge_index``)
+    are left out. All known users are ranked by one lgcn_amd.recommend.topk_rows call."""
+    user_id_map, movie_id_map = data_handler.user_id_map, data_handler.movie_id_map
+    num_users, num_items = len(user_id_map), len(movie_id_map)
+    out: list = [{'error': 'Invalid user ID'} for _ in user_ids]
+    known = [(slot, user_id_map[u]) for slot, u in enumerate(user_ids) if u in user_id_map]
+    if not known:
+        return out
+    dev = model.user_embedding.weight.device
+    users = torch.tensor([u for _, u in known], dtype=torch.int64, device=dev)
+    excl = None
+    if exclude_seen:
+        ei = data_handler.edge_index if train_edge_index is None else train_edge_index
+        ptr, seen = _rec.seen_csr(ei.to(dev), num_users, num_items, by="user")
+        excl = (ptr, seen, users)
+    with torch.no_grad():
+        user_emb, item_emb = model.get_embeddings(user_indices=users, item_indices=torch.arange(num_items, device=dev))
+        idx, score = _rec.topk_rows(user_emb, torch.arange(users.numel()), item_emb, k, excl=excl)
+    id_movie = _id_map(data_handler, "id_movie_map", movie_id_map)
+    title_of = _title_of(data_handler.movies)
+    for (slot, _), row in zip(known, _ranked(idx, score)):
+        out[slot] = [{'movie_id': id_movie[i + num_users], 'title': title_of[id_movie[i + num_users]], 'score': s}
+                     for i, s in row]
+    return out
+
+
+if __name__ == '__main__':
+    from data.dataset_handler import MovieLensDataHandler
+    from models.light_gcn import LightGCN
+
+    handler = MovieLensDataHandler('data/movielens-25m/ratings.csv', 'data/movielens-25m/movies.csv')
+    model = LightGCN(*handler.get_num_users_items()).to('cuda')
+    if os.path.exists('best_model.pth'):
+        model.load_state_dict(torch.load('best_model.pth', map_location='cuda'))
+    model.eval()
+    uid = int(sys.argv[1]) if len(sys.argv) > 1 else next(iter(handler.user_id_map))
+    if uid not in handler.user_id_map:
+        sys.exit(recommend_from_user(model, uid, handler)['error'])
+    train_data, _, _ = handler.get_datasets()
+    ei = train_data.edge_index
+    seen_items = ei[1, ei[0] == handler.user_id_map[uid]] - handler.num_users
+    result = recommend_from_user(model, uid, handler, seen_items)
+    print(f"Top 10 Recommendations for user {uid}:")
+    for rank, rec in enumerate(result['recommendations'], 1):
+        print(f"{rank}. {rec['title']} (Score: {rec['score']:.4f})")
