@@ -650,6 +650,30 @@ int lgcn_select_topk_ranked(const uint32_t* list_key, const int32_t* list_idx, c
                             const int32_t* excl_idx, const int64_t* excl_row, int64_t excl_rows, uint32_t* thr_out,
                             int32_t* out_idx, float* out_score, int32_t* out_n, lgcn_stream_t stream);
 
+/* Full-ranking evaluation counts (added under ABI 11, purely additive): ranked lists plus held-out
+ * sets in, what Recall / Precision / HitRate / NDCG / MRR at several cutoffs are made of out, in
+ * one pass and without leaving the device (one wave per query).
+ *   ranked_idx[q * ld + r], r < k <= ld: query q's candidate at rank r — lgcn_select_topk_ranked's
+ *     out_idx: distinct indices, -1 in the slots a short list could not fill. A negative index is
+ *     never a hit.
+ *   truth: CSR (truth_ptr int64[truth_rows + 1], truth_idx int32 ascending and deduplicated within
+ *     a row) with the row conventions of the exclusion CSR above: query q uses row truth_row[q]
+ *     (row q when truth_row is NULL); a row outside [0, truth_rows) is an empty set.
+ *   cutoffs: a HOST array of n_cutoffs (1..LGCN_METRICS_MAX_CUTOFFS) strictly ascending values in
+ *     [1, k]; they reach the kernel by value (no device allocation, no copy).
+ *   hits_out[q, c]  = ranks r < cutoffs[c] whose index is in the truth row   ([Q, n_cutoffs])
+ *   dcg_out[q, c]   = sum over those ranks of 1 / log2(r + 2), formed and summed in float64 and
+ *                     rounded to float32 once on store: within one float32 ulp of the exact sum,
+ *                     whatever the reduction order                            ([Q, n_cutoffs])
+ *   first_out[q]    = the lowest hit rank in [0, k), -1 if none               ([Q])
+ *   ntruth_out[q]   = the truth row's length (0 for a row outside the CSR)    ([Q])
+ * Q == 0 returns LGCN_OK without a launch. */
+#define LGCN_METRICS_MAX_CUTOFFS 8
+int lgcn_rank_metrics(const int32_t* ranked_idx, int64_t ld, int32_t k, int64_t Q, const int64_t* truth_ptr,
+                      const int32_t* truth_idx, const int64_t* truth_row, int64_t truth_rows, const int32_t* cutoffs,
+                      int32_t n_cutoffs, int32_t* hits_out, float* dcg_out, int32_t* first_out, int32_t* ntruth_out,
+                      lgcn_stream_t stream);
+
 /* Host-only (no GPU): `draws` consecutive numpy legacy np.random.choice(n, size, replace=False)
  * calls (reference utils/train_test.py:187) on the MT19937 state (key[624], *pos) of
  * np.random.get_state(), written to out[draws*size]; key/pos are advanced exactly as numpy would

@@ -85,10 +85,10 @@ def _excl_args(excl, dev, Q: int):
 
 
 def topk_rows(queries: torch.Tensor, picked: torch.Tensor, candidates: torch.Tensor, k: int, excl=None,
-              cap: int | None = None, subset: int | None = None):
-    """(idx int64 [Q, k], score f32 [Q, k]) on the device: for query row queries[picked[q]], the k
-    best rows of ``candidates`` by cosine score that its exclusion row does not name, in rank order
-    (score descending, candidate index ascending; NaN first).
+              cap: int | None = None, subset: int | None = None, index_dtype: torch.dtype = torch.int64):
+    """(idx [Q, k] of ``index_dtype``, int64 by default; score f32 [Q, k]) on the device: for query
+    row queries[picked[q]], the k best rows of ``candidates`` by cosine score that its exclusion row
+    does not name, in rank order (score descending, candidate index ascending; NaN first).
 
     excl: None, or the CSR (ptr, idx) of seen_csr — row q belongs to query q — or (ptr, idx, rows)
     with rows[q] naming the CSR row of query q. Rows are ascending, deduplicated and within [0, M).
@@ -98,8 +98,13 @@ def topk_rows(queries: torch.Tensor, picked: torch.Tensor, candidates: torch.Ten
     candidates) and a query with fewer than k eligible candidates raises ValueError; the filter
     does not know the exclusion rows, so ``cap`` must also hold a query's excluded candidates that
     score above its k-th eligible one (RuntimeError after eight tightening rounds otherwise).
-    Queries are processed in blocks of at most BLOCK_BYTES of list workspace."""
+    Queries are processed in blocks of at most BLOCK_BYTES of list workspace.
+    index_dtype: torch.int64 (the default, what indexing wants) or torch.int32, the kernel's own
+    index buffer handed on unconverted (what lgcn_amd.metrics.rank_metrics reads): a view of the
+    first Q rows of this call's padded buffer, which lives as long as the view does."""
     k = int(k)
+    if index_dtype not in (torch.int64, torch.int32):
+        raise ValueError(f"recommend: index_dtype must be torch.int64 or torch.int32, got {index_dtype}")
     if k < 1 or k > MAX_K:
         raise ValueError(f"recommend: k={k} outside [1, {MAX_K}]")
     cap = CAP if cap is None else int(cap)
@@ -124,7 +129,7 @@ def topk_rows(queries: torch.Tensor, picked: torch.Tensor, candidates: torch.Ten
     Q = picked.numel()
     ptr, eidx, erow, R = _excl_args(excl, dev, Q)
     if Q == 0:
-        return (torch.empty((0, k), dtype=torch.int64, device=dev),
+        return (torch.empty((0, k), dtype=index_dtype, device=dev),
                 torch.empty((0, k), dtype=torch.float32, device=dev))
     Qpad = max(qmul, (Q + qmul - 1) // qmul * qmul)
     dense = M <= cap
@@ -199,7 +204,7 @@ def topk_rows(queries: torch.Tensor, picked: torch.Tensor, candidates: torch.Ten
             ranked(q0, nb, qv, lcnt.data_ptr(), 0, thr.data_ptr(), False)
         else:
             raise RuntimeError("recommend: candidate lists kept overflowing (scores too concentrated for the capacity)")
-    return out_idx[:Q].to(torch.int64), out_score[:Q].clone()
+    return (out_idx[:Q].to(torch.int64) if index_dtype == torch.int64 else out_idx[:Q]), out_score[:Q].clone()
 
 
 def topk_items(user_emb: torch.Tensor, item_emb: torch.Tensor, users, k: int, seen=None, **kw):

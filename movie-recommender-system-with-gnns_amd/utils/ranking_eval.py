@@ -1,0 +1,36 @@
+"""Full-ranking evaluation of a model (not in the reference, whose Recall@k in utils/train_test.py
+is a sampled one and stays as it is): Recall / Precision / HitRate / NDCG / MRR at several cutoffs
+over every user with held-out items, on the HIP path of lgcn_amd.metrics.
+
+    from utils.ranking_eval import evaluate_ranking
+    evaluate_ranking(model, train_data.edge_index, test_data.edge_index, 'cuda', ks=(10, 20))
+"""
+import torch
+
+
+def evaluate_ranking(model: torch.nn.Module, train_edge_index: torch.Tensor, heldout_edge_index: torch.Tensor,
+                     device, ks=(20,), embeddings: str = "raw") -> dict:
+    """Every user with a held-out edge gets all items ranked, the items of their training edges left
+    out, and the means of recall / precision / hit_rate / ndcg / mrr at each cutoff of ``ks`` come
+    back as lgcn_amd.metrics.summarize's dict ({'users': n, 'recall@20': ..., ...}).
+    Both edge sets use the project's global numbering (items at num_users + i), either direction.
+    embeddings="raw" ranks the rows of model.get_embeddings — what utils.recommend serves, so the
+    number describes the lists users get; "propagated" ranks model(train_edge_index)'s outputs, the
+    LightGCN paper's protocol. Runs on the HIP path: the model must be on a ROCm device."""
+    if embeddings not in ("raw", "propagated"):
+        raise ValueError(f"evaluate_ranking: embeddings must be 'raw' or 'propagated', got {embeddings!r}")
+    from lgcn_amd import metrics
+    from lgcn_amd.recommend import seen_csr
+
+    model.eval()
+    U, I = model.num_users, model.num_items
+    with torch.no_grad():
+        train_edge_index = train_edge_index.to(device)
+        seen = seen_csr(train_edge_index, U, I, by="user")
+        truth = seen_csr(heldout_edge_index.to(device), U, I, by="user")
+        if embeddings == "raw":
+            user_emb, item_emb = model.get_embeddings(user_indices=torch.arange(U, device=device),
+                                                      item_indices=torch.arange(I, device=device))
+        else:
+            user_emb, item_emb = model(train_edge_index)
+        return metrics.evaluate_ranking(user_emb, item_emb, truth, ks=ks, seen=seen)

@@ -11,6 +11,9 @@ come in ascending index order. ``recommend_for_users`` serves a batch of users i
 Not carried over: the plotting (``visualizations``) and the import-time seeding (nothing here draws
 random numbers). Unknown ids are answered without touching the GPU; everything else needs the model
 on a ROCm device (lgcn_amd._ffi.LgcnError otherwise, there is no CPU fallback).
+How good the served lists are (full-ranking Recall / Precision / HitRate / NDCG / MRR, the same raw
+rows, training items left out):
+    utils.ranking_eval.evaluate_ranking(model, train_data.edge_index, test_data.edge_index, 'cuda', ks=(10, 20))
 """
 from typing import Any, Dict, List, Optional, Sequence, Union
 
