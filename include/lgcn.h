@@ -674,6 +674,37 @@ int lgcn_rank_metrics(const int32_t* ranked_idx, int64_t ld, int32_t k, int64_t 
                       int32_t n_cutoffs, int32_t* hits_out, float* dcg_out, int32_t* first_out, int32_t* ntruth_out,
                       lgcn_stream_t stream);
 
+/* Greedy Maximal Marginal Relevance re-ranking of per-query candidate pools (added under ABI 11,
+ * purely additive): k picks from a pool of N, each the best trade of relevance against similarity
+ * to the picks before it, with what intra-list diversity is made of. One wave per query, the pool's
+ * unit rows staged once in LDS (csrc/lgcn_rerank.hip).
+ *   pool_idx[q * ld + p], pool_score[q * ld + p], p < N <= ld: query q's pool in the caller's order
+ *     (lgcn_select_topk_ranked's rank order in practice), entries distinct. An entry is eligible
+ *     when 0 <= index < M; anything else (-1 of a short list, any out-of-range value) is skipped
+ *     and its row is never read.
+ *   Cn: [M, D] unit rows as lgcn_normalize_rows writes them, 16-byte aligned, D a multiple of 4
+ *     (lgcn_recall_width's widths are).
+ *   rule, with d = diversity in [0, 1]: every eligible position keeps m_p, its largest similarity
+ *     to a pick so far (0 before the first pick), and a_p, the sum of those similarities (0 at
+ *     first). Step t = 0 .. k - 1: the value of an eligible, not yet picked position is
+ *     (1.f - d) * r_p - d * m_p in f32 as written (two products, one subtraction; NaN counts as
+ *     -inf); the pick p* has the largest value, the lowest pool position among equal values.
+ *     out_idx[q, t] = its index, out_score[q, t] = r_p*, out_pair[q, t] = a_p*. Then, for every
+ *     remaining eligible position, s = Cn[i_p] . Cn[i_p*] in f32 (summation order unspecified),
+ *     m_p = s after the first pick and fmaxf(m_p, s) afterwards, a_p += s.
+ *     With no eligible position left, slots t .. k - 1 get -1 / -inf / 0. out_n[q] = filled slots.
+ *   So d = 0 returns the eligible entries in pool order, and the list for k' < k is the prefix of
+ *   the list for k. out_idx, out_score, out_pair are [Q, k], out_n is [Q].
+ * LGCN_E_ARG: a null pointer, k outside [1, N], N > ld, Q < 0, M < 0, D < 1 or not a multiple of 4,
+ * a misaligned Cn, d outside [0, 1] or NaN. LGCN_E_UNSUPPORTED: N > LGCN_MMR_MAX_POOL, or
+ * N * D * 4 > LGCN_MMR_MAX_LDS_BYTES (the pool's rows do not fit the LDS budget). Checked before
+ * any HIP call; Q == 0 returns LGCN_OK without a launch. Allocates nothing, does not synchronise. */
+#define LGCN_MMR_MAX_POOL 512
+#define LGCN_MMR_MAX_LDS_BYTES 131072
+int lgcn_rerank_mmr(const int32_t* pool_idx, const float* pool_score, int64_t ld, int32_t N, int64_t Q,
+                    const float* Cn, int64_t M, int32_t D, int32_t k, float diversity, int32_t* out_idx,
+                    float* out_score, float* out_pair, int32_t* out_n, lgcn_stream_t stream);
+
 /* Host-only (no GPU): `draws` consecutive numpy legacy np.random.choice(n, size, replace=False)
  * calls (reference utils/train_test.py:187) on the MT19937 state (key[624], *pos) of
  * np.random.get_state(), written to out[draws*size]; key/pos are advanced exactly as numpy would

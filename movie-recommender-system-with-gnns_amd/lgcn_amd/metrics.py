@@ -15,6 +15,9 @@ the lowest hit rank ``first``:
                                 IDCG_c = sum over r < min(c, T) of 1 / log2(r + 2)
     mrr@c    = 1 / (first + 1) if 0 <= first < c else 0
 each averaged over the users with T > 0 (``users`` in the result).
+With evaluate_ranking(diversity=...) the lists are recommend.topk_rows_diverse's (greedy MMR over a
+relevance pool) and the result also carries ild@c, the mean intra-list diversity
+(recommend.intra_list_diversity) over the evaluated users with at least two listed items.
 """
 from __future__ import annotations
 
@@ -148,7 +151,7 @@ def summarize(counts, ks) -> dict:
 
 
 def evaluate_ranking(user_emb: torch.Tensor, item_emb: torch.Tensor, truth, ks=(20,), seen=None, users=None,
-                     **topk_kw) -> dict:
+                     diversity: float | None = None, pool: int | None = None, **topk_kw) -> dict:
     """Full-ranking evaluation of an embedding pair: summarize's dict.
 
     truth: the held-out CSR over all users, (ptr, idx) as recommend.seen_csr(heldout_edges, U, I)
@@ -158,13 +161,37 @@ def evaluate_ranking(user_emb: torch.Tensor, item_emb: torch.Tensor, truth, ks=(
     One recommend.topk_items call for max(ks) items per user, one lgcn_rank_metrics launch, then
     summarize. Host reads: summarize's one; topk_rows' one per query block when the items exceed
     its dense capacity; and, when ``users`` is left to default, the size of torch.nonzero's result
-    (pass ``users`` to avoid it — users without truth are left out of the means either way)."""
+    (pass ``users`` to avoid it — users without truth are left out of the means either way).
+
+    diversity: None evaluates the relevance lists (the keys above, nothing else). A float in [0, 1]
+    evaluates what recommend.topk_rows_diverse serves instead — each user's pool of ``pool`` entries
+    (its default when None) re-ranked by greedy MMR down to max(ks); 0.0 keeps the relevance lists
+    and only measures — and the result also carries 'ild@c' for every cutoff: the mean of
+    recommend.intra_list_diversity over the evaluated users (non-empty truth row) with at least two
+    listed items, nan when there is none. One more host read."""
     cs = _cutoffs(ks)
+    if diversity is None and pool is not None:
+        raise ValueError("evaluate_ranking: pool is the re-rank's pool and needs diversity")
+    if diversity is not None:
+        diversity = recommend._diversity(diversity)
     _ffi.require_device(user_emb, "evaluate_ranking")
     dev = user_emb.device
     ptr, idx = truth[0].to(dev), truth[1].to(dev)
     if users is None:
         users = torch.nonzero(ptr[1:] > ptr[:-1]).view(-1)
     users = torch.as_tensor(users).to(device=dev, dtype=torch.int64).view(-1)
+    if diversity is not None:
+        excl = None if seen is None else (seen[0], seen[1], users)
+        lists = recommend.topk_rows_diverse(user_emb, users, item_emb, cs[-1], diversity, pool=pool, excl=excl,
+                                            index_dtype=torch.int32, **topk_kw)
+        counts = rank_metrics(lists.idx, (ptr, idx), cs, rows=users)
+        out = summarize(counts, cs)
+        ild = recommend.intra_list_diversity(lists.pair, lists.n, cs)
+        listed = (counts.n_truth > 0)[:, None] & ~torch.isnan(ild)
+        sums = torch.where(listed, ild, torch.zeros((), dtype=ild.dtype, device=dev)).sum(0)
+        flat = torch.cat([sums, listed.sum(0).to(ild.dtype)]).tolist()  # the host read
+        for j, cv in enumerate(cs):
+            out[f"ild@{cv}"] = flat[j] / flat[len(cs) + j] if flat[len(cs) + j] else float("nan")
+        return out
     ranked, _ = recommend.topk_items(user_emb, item_emb, users, cs[-1], seen=seen, index_dtype=torch.int32, **topk_kw)
     return summarize(rank_metrics(ranked, (ptr, idx), cs, rows=users), cs)

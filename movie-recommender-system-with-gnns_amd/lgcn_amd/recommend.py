@@ -17,10 +17,16 @@ Ranking rule: score descending, then candidate index ascending (NaN scores first
 is formed from eligible subset entries only: it is then the k-th best of a subset of the eligible
 candidates, so it is a lower bound of the k-th best eligible score of all M, and the filtered list
 holds the whole eligible top k whatever was excluded.
+
+Diversity on top of relevance (csrc/lgcn_rerank.hip, one wave per query, the pool's rows in LDS):
+    rerank_mmr            greedy Maximal Marginal Relevance over per-query pools   lgcn_rerank_mmr
+    topk_rows_diverse     topk_rows for a pool, then rerank_mmr down to k
+    intra_list_diversity  ILD@c from rerank_mmr's pair sums (plain torch)
 """
 from __future__ import annotations
 
 import ctypes
+from typing import NamedTuple
 
 import torch
 
@@ -36,6 +42,9 @@ CAP = 16384
 SUBSET_MIN = 2048
 SUBSET_PER_K = 16
 MAX_K = _ffi.RANKED_MAX_K
+# the re-rank kernel's pool: entries per query, and bytes of pool rows (N * D * 4) it stages in LDS
+MMR_MAX_POOL = _ffi.MMR_MAX_POOL
+MMR_MAX_LDS_BYTES = _ffi.MMR_MAX_LDS_BYTES
 
 
 def seen_csr(edge_index: torch.Tensor, num_users: int, num_items: int, by: str = "user"):
@@ -205,6 +214,153 @@ def topk_rows(queries: torch.Tensor, picked: torch.Tensor, candidates: torch.Ten
         else:
             raise RuntimeError("recommend: candidate lists kept overflowing (scores too concentrated for the capacity)")
     return (out_idx[:Q].to(torch.int64) if index_dtype == torch.int64 else out_idx[:Q]), out_score[:Q].clone()
+
+
+class Reranked(NamedTuple):
+    """lgcn_rerank_mmr's outputs for Q queries and k picks, on the device."""
+    idx: torch.Tensor    # [Q, k], the pool's index dtype: the picks in pick order, -1 in unfilled slots
+    score: torch.Tensor  # f32 [Q, k]: each pick's relevance as the pool gave it, -inf in unfilled slots
+    pair: torch.Tensor   # f32 [Q, k]: each pick's summed similarity to the picks before it, 0 in unfilled slots
+    n: torch.Tensor      # int32 [Q]: filled slots
+
+
+def _diversity(diversity) -> float:
+    d = float(diversity)
+    if not 0.0 <= d <= 1.0:  # NaN fails both comparisons
+        raise ValueError(f"recommend: diversity={d} outside [0, 1]")
+    return d
+
+
+def _width(d: int) -> int:
+    """lgcn_recall_width's D for rows of d columns, formed on the host (nothing is loaded)."""
+    if d < 1 or d > 256:
+        raise ValueError(f"recommend: rows of {d} columns (1 to 256 are supported)")
+    D = 8
+    while D < d:
+        D <<= 1
+    return D
+
+
+def rerank_mmr(pool_idx: torch.Tensor, pool_score: torch.Tensor, candidates: torch.Tensor, k: int, diversity: float,
+               normalized: bool = False) -> Reranked:
+    """Greedy Maximal Marginal Relevance over per-query pools, on the device (lgcn_rerank_mmr).
+
+    pool_idx [Q, N] int32 or int64 and pool_score [Q, N] f32: each query's pool in the caller's
+    order (topk_rows' output in practice; rows may be a column slice of a wider tensor), entries
+    distinct; an entry outside [0, M) — the -1 of a short list — is skipped. candidates [M, d]: the
+    rows the similarities are cosines of, normalised once here; with normalized=True they are taken
+    as unit rows already and only zero-padded to the kernel's width.
+    Step by step the pick is the unpicked entry with the largest
+    (1 - diversity) * score - diversity * (largest cosine to a pick so far), the lowest pool
+    position among equal values; so diversity=0 returns the pool's first k eligible entries and the
+    list for a smaller k is a prefix. Returns Reranked(idx, score, pair, n); intra_list_diversity
+    turns pair and n into ILD@c.
+    Limits: 1 <= k <= N <= MMR_MAX_POOL and N * D * 4 <= MMR_MAX_LDS_BYTES, D the padded width
+    (ValueError before anything is loaded)."""
+    k, diversity = int(k), _diversity(diversity)
+    if pool_idx.dim() != 2 or pool_score.shape != pool_idx.shape:
+        raise ValueError("rerank_mmr: pool_idx and pool_score must both be [Q, N]")
+    if pool_idx.dtype not in (torch.int32, torch.int64):
+        raise TypeError(f"rerank_mmr: pool_idx must be int32 or int64, got {pool_idx.dtype}")
+    if pool_score.dtype != torch.float32:
+        raise TypeError(f"rerank_mmr: pool_score must be float32, got {pool_score.dtype}")
+    if candidates.dim() != 2 or candidates.dtype != torch.float32:
+        raise TypeError("rerank_mmr: candidates must be 2-D float32")
+    Q, N = pool_idx.shape
+    M, d = candidates.shape
+    if k < 1 or k > N:
+        raise ValueError(f"rerank_mmr: k={k} outside [1, N={N}]")
+    if N > MMR_MAX_POOL:
+        raise ValueError(f"rerank_mmr: a pool of {N} entries exceeds MMR_MAX_POOL={MMR_MAX_POOL}")
+    D = _width(d)
+    if N * D * 4 > MMR_MAX_LDS_BYTES:
+        raise ValueError(f"rerank_mmr: {N} pool rows of width {D} take {N * D * 4} bytes, above "
+                         f"MMR_MAX_LDS_BYTES={MMR_MAX_LDS_BYTES} (at most {MMR_MAX_LDS_BYTES // (4 * D)} rows)")
+    lib = _ffi.load()
+    for t in (pool_idx, pool_score, candidates):
+        _ffi.require_device(t, "rerank_mmr")
+    dev = pool_idx.device
+    index_dtype = pool_idx.dtype
+    if index_dtype == torch.int64:  # a value outside int32 cannot be a candidate: skipped, not wrapped
+        fits = (pool_idx >= 0) & (pool_idx <= torch.iinfo(torch.int32).max)
+        pool_idx = torch.where(fits, pool_idx, -1).to(torch.int32)
+    pool_score = pool_score.detach()
+    if not (pool_idx.stride(1) == 1 and pool_score.stride(1) == 1 and pool_idx.stride(0) >= N
+            and (Q <= 1 or pool_idx.stride(0) == pool_score.stride(0))):  # one leading dimension serves both
+        pool_idx, pool_score = pool_idx.contiguous(), pool_score.contiguous()
+    ld = pool_idx.stride(0) if Q > 1 else N  # a single row's stride means nothing
+    s = _ffi.stream_of(dev)
+    candidates = candidates.detach()
+    if normalized and d == D and candidates.is_contiguous() and candidates.data_ptr() % 16 == 0 and M > 0:
+        Cn = candidates
+    else:
+        Cn = torch.zeros((max(M, 1), D), dtype=torch.float32, device=dev)
+        if normalized:
+            Cn[:M, :d] = candidates
+        else:
+            _normalize_into(lib, candidates, None, M, Cn.data_ptr(), D, M, s)
+    out_idx = torch.empty((Q, k), dtype=torch.int32, device=dev)
+    out_score = torch.empty((Q, k), dtype=torch.float32, device=dev)
+    out_pair = torch.empty((Q, k), dtype=torch.float32, device=dev)
+    out_n = torch.empty(Q, dtype=torch.int32, device=dev)
+    if Q:
+        _ffi.check(lib.lgcn_rerank_mmr(pool_idx.data_ptr(), pool_score.data_ptr(), ld, N, Q, Cn.data_ptr(), M, D, k,
+                                       diversity, out_idx.data_ptr(), out_score.data_ptr(), out_pair.data_ptr(),
+                                       out_n.data_ptr(), s), "lgcn_rerank_mmr")
+    return Reranked(out_idx.to(index_dtype), out_score, out_pair, out_n)
+
+
+def topk_rows_diverse(queries: torch.Tensor, picked: torch.Tensor, candidates: torch.Tensor, k: int, diversity: float,
+                      pool: int | None = None, excl=None, **kw) -> Reranked:
+    """topk_rows for a relevance pool of ``pool`` entries per query, then rerank_mmr down to k:
+    Reranked(idx, score, pair, n), score staying the cosine relevance.
+
+    pool: default max(4 * k, 64); whatever is asked for is clamped to what exists and what the
+    re-rank kernel holds, min(M, MMR_MAX_POOL, MMR_MAX_LDS_BYTES // (4 * D)) with D the padded
+    width, and a pool that ends up below k is a ValueError. excl and kw (cap, subset, index_dtype)
+    are topk_rows'."""
+    k, diversity = int(k), _diversity(diversity)
+    if k < 1:
+        raise ValueError(f"recommend: k={k} outside [1, {MMR_MAX_POOL}]")
+    if queries.dim() != 2 or candidates.dim() != 2:
+        raise ValueError("recommend: queries and candidates must be 2-D")
+    M, D = candidates.shape[0], _width(candidates.shape[1])
+    want = max(4 * k, 64) if pool is None else int(pool)
+    limits = {"the candidate count M": M, "MMR_MAX_POOL": MMR_MAX_POOL,
+              f"MMR_MAX_LDS_BYTES // (4 * D) at D={D}": MMR_MAX_LDS_BYTES // (4 * D)}
+    name = min(limits, key=limits.get)
+    pool = min(want, limits[name])
+    if pool < k:
+        if want < k:
+            raise ValueError(f"recommend: pool={want} is below k={k}")
+        raise ValueError(f"recommend: k={k} exceeds the largest pool, {limits[name]} ({name})")
+    index_dtype = kw.pop("index_dtype", torch.int64)
+    if index_dtype not in (torch.int64, torch.int32):
+        raise ValueError(f"recommend: index_dtype must be torch.int64 or torch.int32, got {index_dtype}")
+    idx, score = topk_rows(queries, picked, candidates, pool, excl=excl, index_dtype=torch.int32, **kw)
+    out = rerank_mmr(idx, score, candidates, k, diversity)
+    return out if index_dtype == torch.int32 else out._replace(idx=out.idx.to(torch.int64))
+
+
+def intra_list_diversity(pair: torch.Tensor, n: torch.Tensor, ks) -> torch.Tensor:
+    """ILD@c of re-ranked lists, float64 [Q, C] for the sorted distinct cutoffs of ``ks``: one minus
+    the mean pairwise cosine among a list's first c' = min(c, n) items,
+    1 - 2 * sum(pair[:c']) / (c' * (c' - 1)), NaN where c' < 2. pair and n are Reranked's (pair[t]
+    is pick t's summed cosine to picks 0 .. t - 1). Plain torch on the tensors' device; CPU tensors
+    work too."""
+    if pair.dim() != 2 or n.shape != pair.shape[:1]:
+        raise ValueError(f"intra_list_diversity: pair {tuple(pair.shape)} / n {tuple(n.shape)} are not [Q, k] / [Q]")
+    cs = sorted({int(c) for c in ks})
+    if not cs or cs[0] < 1 or cs[-1] > pair.shape[1]:
+        raise ValueError(f"intra_list_diversity: cutoffs {cs} outside [1, k={pair.shape[1]}]")
+    f64 = torch.float64
+    csum = torch.cat([torch.zeros((pair.shape[0], 1), dtype=f64, device=pair.device),
+                      torch.cumsum(pair.to(f64), 1)], 1)
+    c = torch.tensor(cs, dtype=torch.int64, device=pair.device)
+    cp = torch.minimum(n.to(torch.int64).clamp(min=0)[:, None], c[None, :])
+    pairs = (cp * (cp - 1)).to(f64)
+    ild = 1.0 - 2.0 * csum.gather(1, cp) / pairs.clamp(min=1.0)
+    return torch.where(cp >= 2, ild, torch.full((), float("nan"), dtype=f64, device=pair.device))
 
 
 def topk_items(user_emb: torch.Tensor, item_emb: torch.Tensor, users, k: int, seen=None, **kw):

@@ -9,14 +9,17 @@ import torch
 
 
 def evaluate_ranking(model: torch.nn.Module, train_edge_index: torch.Tensor, heldout_edge_index: torch.Tensor,
-                     device, ks=(20,), embeddings: str = "raw") -> dict:
+                     device, ks=(20,), embeddings: str = "raw", diversity=None, pool=None) -> dict:
     """Every user with a held-out edge gets all items ranked, the items of their training edges left
     out, and the means of recall / precision / hit_rate / ndcg / mrr at each cutoff of ``ks`` come
     back as lgcn_amd.metrics.summarize's dict ({'users': n, 'recall@20': ..., ...}).
     Both edge sets use the project's global numbering (items at num_users + i), either direction.
     embeddings="raw" ranks the rows of model.get_embeddings — what utils.recommend serves, so the
     number describes the lists users get; "propagated" ranks model(train_edge_index)'s outputs, the
-    LightGCN paper's protocol. Runs on the HIP path: the model must be on a ROCm device."""
+    LightGCN paper's protocol. Runs on the HIP path: the model must be on a ROCm device.
+    diversity / pool: lgcn_amd.metrics.evaluate_ranking's — None evaluates the relevance lists; a
+    float in [0, 1] evaluates the MMR re-ranked lists utils.recommend.recommend_for_users serves with
+    the same arguments and adds 'ild@c' (intra-list diversity) per cutoff; 0.0 only measures."""
     if embeddings not in ("raw", "propagated"):
         raise ValueError(f"evaluate_ranking: embeddings must be 'raw' or 'propagated', got {embeddings!r}")
     from lgcn_amd import metrics
@@ -33,4 +36,4 @@ def evaluate_ranking(model: torch.nn.Module, train_edge_index: torch.Tensor, hel
                                                       item_indices=torch.arange(I, device=device))
         else:
             user_emb, item_emb = model(train_edge_index)
-        return metrics.evaluate_ranking(user_emb, item_emb, truth, ks=ks, seen=seen)
+        return metrics.evaluate_ranking(user_emb, item_emb, truth, ks=ks, seen=seen, diversity=diversity, pool=pool)

@@ -7,7 +7,8 @@ shapes: {'recommendations': [{'title', 'score'} x 10]}, {'top_users': [{'user_id
 or {'error': 'Invalid user ID' / 'Invalid movie ID'}; fewer than ten entries when fewer candidates
 are left. Where the reference sorts a dense score row and walks it in Python, one
 lgcn_amd.recommend.topk_rows call with a one-row exclusion CSR ranks on the device; equal scores
-come in ascending index order. ``recommend_for_users`` serves a batch of users in one call.
+come in ascending index order. ``recommend_for_users`` serves a batch of users in one call, with
+``diversity=`` a list re-ranked for diversity (greedy MMR over a relevance pool, on the device).
 Not carried over: the plotting (``visualizations``) and the import-time seeding (nothing here draws
 random numbers). Unknown ids are answered without touching the GPU; everything else needs the model
 on a ROCm device (lgcn_amd._ffi.LgcnError otherwise, there is no CPU fallback).
@@ -102,12 +103,19 @@ def recommend_from_movie(model: torch.nn.Module, movie_id: int, data_handler: An
 
 
 def recommend_for_users(model: torch.nn.Module, user_ids: Sequence[int], data_handler: Any, k: int = 10,
-                        exclude_seen: bool = True, train_edge_index: Optional[torch.Tensor] = None
+                        exclude_seen: bool = True, train_edge_index: Optional[torch.Tensor] = None,
+                        diversity: Optional[float] = None, pool: Optional[int] = None
                         ) -> List[Union[Dict[str, str], List[Dict[str, Union[int, str, float]]]]]:
     """One entry per id of ``user_ids``: the user's k best movies as [{'movie_id', 'title', 'score'}],
     or {'error': 'Invalid user ID'} for an unknown id. With ``exclude_seen`` the movies a user has an
     edge to in ``train_edge_index`` (default: every edge the handler holds, ``data_handler.edge_index``)
-    are left out. All known users are ranked by one lgcn_amd.recommend.topk_rows call."""
+    are left out. All known users are ranked by one lgcn_amd.recommend.topk_rows call.
+    ``diversity`` (a float in [0, 1]; None: relevance only, as above) serves
+    lgcn_amd.recommend.topk_rows_diverse's lists instead: each user's ``pool`` most relevant movies
+    (its default when None) re-ranked by greedy Maximal Marginal Relevance down to k, in pick order;
+    'score' stays the cosine relevance, so it no longer descends along a list."""
+    if diversity is None and pool is not None:
+        raise ValueError("recommend_for_users: pool is the re-rank's pool and needs diversity")
     user_id_map, movie_id_map = data_handler.user_id_map, data_handler.movie_id_map
     num_users, num_items = len(user_id_map), len(movie_id_map)
     out: list = [{'error': 'Invalid user ID'} for _ in user_ids]
@@ -123,7 +131,11 @@ def recommend_for_users(model: torch.nn.Module, user_ids: Sequence[int], data_ha
         excl = (ptr, seen, users)
     with torch.no_grad():
         user_emb, item_emb = model.get_embeddings(user_indices=users, item_indices=torch.arange(num_items, device=dev))
-        idx, score = _rec.topk_rows(user_emb, torch.arange(users.numel()), item_emb, k, excl=excl)
+        if diversity is None:
+            idx, score = _rec.topk_rows(user_emb, torch.arange(users.numel()), item_emb, k, excl=excl)
+        else:
+            idx, score = _rec.topk_rows_diverse(user_emb, torch.arange(users.numel()), item_emb, k, diversity,
+                                                pool=pool, excl=excl)[:2]
     id_movie = _id_map(data_handler, "id_movie_map", movie_id_map)
     title_of = _title_of(data_handler.movies)
     for (slot, _), row in zip(known, _ranked(idx, score)):
