@@ -705,6 +705,43 @@ int lgcn_rerank_mmr(const int32_t* pool_idx, const float* pool_score, int64_t ld
                     const float* Cn, int64_t M, int32_t D, int32_t k, float diversity, int32_t* out_idx,
                     float* out_score, float* out_pair, int32_t* out_n, lgcn_stream_t stream);
 
+/* "Because you watched" evidence for recommended items (added under ABI 11, purely additive): for
+ * every recommended slot of a query, the r items of the query's history that contribute most to it.
+ * The query's k candidate rows are staged once in LDS and its history is streamed past them, by one
+ * wave, or by eight when the history is long (csrc/lgcn_explain.hip).
+ *   rec_idx[q * ld + t], t < k <= ld: query q's recommended candidate in slot t
+ *     (lgcn_select_topk_ranked's or lgcn_rerank_mmr's out_idx). A value outside [0, M), such as the
+ *     -1 of a short list, marks an empty slot.
+ *   history: CSR (hist_ptr int64[hist_rows + 1], hist_idx int32 ascending and distinct within a row)
+ *     with the row conventions of the exclusion and truth CSRs above: query q uses row hist_row[q]
+ *     (row q when hist_row is NULL); a row outside [0, hist_rows) is an empty history. Rows may be
+ *     arbitrarily long. hist_w (nullable): one f32 weight per CSR entry, NULL meaning 1.
+ *   Cn: [M, D] rows as lgcn_normalize_rows writes them, 16-byte aligned, D a multiple of 4 and at
+ *     most 256 (k * D * 4 <= 64 KiB of LDS at the limits).
+ *   rule, per (q, t) with j the slot's candidate: history entry e with i = hist_idx[e] is eligible
+ *     when 0 <= i < M and i != j (a row is never a reason for itself). Its contribution is
+ *     c_e = hist_w[e] * (Cn[i] . Cn[j]): the dot in f32 (summation order unspecified), then one f32
+ *     multiplication (none when hist_w is NULL). The eligible entries are ranked by c descending,
+ *     then item index ascending; NaN ranks as -inf (and -0 as +0).
+ *   out_idx[q, t, 0:r], out_val[q, t, 0:r]: the first min(r, eligible) entries as (item index, c as
+ *     computed; a NaN is stored as NaN, a -0 as +0); out_n[q, t] that count; unfilled positions hold
+ *     -1 / -inf. out_sum[q, t] (nullable pointer): the f32 sum of c over ALL eligible entries, 0
+ *     when there are none (summation order unspecified). An empty slot gives n = 0, -1 / -inf, sum 0.
+ *   So the list for r' < r is the prefix of the list for r. out_idx, out_val are [Q, k, r], out_n
+ *   and out_sum [Q, k].
+ * LGCN_E_ARG: a null required pointer (hist_w, hist_row, out_sum may be NULL), k outside [1, ld],
+ * r < 1, Q < 0, M < 0, hist_rows < 0, D < 1, above 256 or not a multiple of 4, a misaligned Cn.
+ * LGCN_E_UNSUPPORTED: k > LGCN_EXPLAIN_MAX_K, r > LGCN_EXPLAIN_MAX_R. Checked before any HIP call;
+ * Q == 0 returns LGCN_OK without a launch. Allocates nothing, does not synchronise. */
+#define LGCN_EXPLAIN_MAX_K 64   /* recommended slots per query */
+#define LGCN_EXPLAIN_MAX_R 8    /* reasons per slot */
+int lgcn_explain_topr(const int32_t* rec_idx, int64_t ld, int32_t k, int64_t Q,
+                      const int64_t* hist_ptr, const int32_t* hist_idx, const float* hist_w,
+                      const int64_t* hist_row, int64_t hist_rows,
+                      const float* Cn, int64_t M, int32_t D, int32_t r,
+                      int32_t* out_idx, float* out_val, int32_t* out_n, float* out_sum,
+                      lgcn_stream_t stream);
+
 /* Host-only (no GPU): `draws` consecutive numpy legacy np.random.choice(n, size, replace=False)
  * calls (reference utils/train_test.py:187) on the MT19937 state (key[624], *pos) of
  * np.random.get_state(), written to out[draws*size]; key/pos are advanced exactly as numpy would

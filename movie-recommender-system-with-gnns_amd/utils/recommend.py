@@ -8,7 +8,9 @@ or {'error': 'Invalid user ID' / 'Invalid movie ID'}; fewer than ten entries whe
 are left. Where the reference sorts a dense score row and walks it in Python, one
 lgcn_amd.recommend.topk_rows call with a one-row exclusion CSR ranks on the device; equal scores
 come in ascending index order. ``recommend_for_users`` serves a batch of users in one call, with
-``diversity=`` a list re-ranked for diversity (greedy MMR over a relevance pool, on the device).
+``diversity=`` a list re-ranked for diversity (greedy MMR over a relevance pool, on the device) and
+with ``explain=r`` every movie carrying the r movies of the user's history that point at it most
+strongly ('because', lgcn_amd.explain on the device).
 Not carried over: the plotting (``visualizations``) and the import-time seeding (nothing here draws
 random numbers). Unknown ids are answered without touching the GPU; everything else needs the model
 on a ROCm device (lgcn_amd._ffi.LgcnError otherwise, there is no CPU fallback).
@@ -26,6 +28,7 @@ if __name__ == '__main__':  # run as a script: the package root (this file's par
 
     sys.path.insert(0, os.path.abspath(os.path.join(os.path.dirname(os.path.abspath(__file__)), '..')))
 
+from lgcn_amd import explain as _explain
 from lgcn_amd import recommend as _rec
 
 TOP_N = 10  # the reference's list length
@@ -104,8 +107,9 @@ def recommend_from_movie(model: torch.nn.Module, movie_id: int, data_handler: An
 
 def recommend_for_users(model: torch.nn.Module, user_ids: Sequence[int], data_handler: Any, k: int = 10,
                         exclude_seen: bool = True, train_edge_index: Optional[torch.Tensor] = None,
-                        diversity: Optional[float] = None, pool: Optional[int] = None
-                        ) -> List[Union[Dict[str, str], List[Dict[str, Union[int, str, float]]]]]:
+                        diversity: Optional[float] = None, pool: Optional[int] = None,
+                        explain: Optional[int] = None
+                        ) -> List[Union[Dict[str, str], List[Dict[str, Any]]]]:
     """One entry per id of ``user_ids``: the user's k best movies as [{'movie_id', 'title', 'score'}],
     or {'error': 'Invalid user ID'} for an unknown id. With ``exclude_seen`` the movies a user has an
     edge to in ``train_edge_index`` (default: every edge the handler holds, ``data_handler.edge_index``)
@@ -113,9 +117,19 @@ def recommend_for_users(model: torch.nn.Module, user_ids: Sequence[int], data_ha
     ``diversity`` (a float in [0, 1]; None: relevance only, as above) serves
     lgcn_amd.recommend.topk_rows_diverse's lists instead: each user's ``pool`` most relevant movies
     (its default when None) re-ranked by greedy Maximal Marginal Relevance down to k, in pick order;
-    'score' stays the cosine relevance, so it no longer descends along a list."""
+    'score' stays the cosine relevance, so it no longer descends along a list.
+    ``explain`` (an int r in [1, lgcn_amd.explain.MAX_R]; None: today's dictionaries, no new key) adds
+    'because': [{'movie_id', 'title', 'similarity'}] to every movie: the at most r movies the user has
+    an edge to — in the same edge set ``exclude_seen`` uses, whether or not it is set — whose rows have
+    the largest cosine to the recommended movie's row, best first (lgcn_amd.explain.explain_items on
+    the rows the list was ranked with); fewer than r for a shorter history. It explains the re-ranked
+    list when ``diversity`` is set."""
     if diversity is None and pool is not None:
         raise ValueError("recommend_for_users: pool is the re-rank's pool and needs diversity")
+    if explain is not None:
+        explain = int(explain)
+        if explain < 1 or explain > _explain.MAX_R:
+            raise ValueError(f"recommend_for_users: explain={explain} outside [1, {_explain.MAX_R}]")
     user_id_map, movie_id_map = data_handler.user_id_map, data_handler.movie_id_map
     num_users, num_items = len(user_id_map), len(movie_id_map)
     out: list = [{'error': 'Invalid user ID'} for _ in user_ids]
@@ -124,11 +138,12 @@ def recommend_for_users(model: torch.nn.Module, user_ids: Sequence[int], data_ha
         return out
     dev = model.user_embedding.weight.device
     users = torch.tensor([u for _, u in known], dtype=torch.int64, device=dev)
-    excl = None
-    if exclude_seen:
+    excl = history = None
+    if exclude_seen or explain is not None:
         ei = data_handler.edge_index if train_edge_index is None else train_edge_index
-        ptr, seen = _rec.seen_csr(ei.to(dev), num_users, num_items, by="user")
-        excl = (ptr, seen, users)
+        history = _rec.seen_csr(ei.to(dev), num_users, num_items, by="user")
+        if exclude_seen:
+            excl = (history[0], history[1], users)
     with torch.no_grad():
         user_emb, item_emb = model.get_embeddings(user_indices=users, item_indices=torch.arange(num_items, device=dev))
         if diversity is None:
@@ -136,11 +151,21 @@ def recommend_for_users(model: torch.nn.Module, user_ids: Sequence[int], data_ha
         else:
             idx, score = _rec.topk_rows_diverse(user_emb, torch.arange(users.numel()), item_emb, k, diversity,
                                                 pool=pool, excl=excl)[:2]
+        why = None if explain is None else _explain.explain_items(item_emb, users, idx, history, r=explain)
     id_movie = _id_map(data_handler, "id_movie_map", movie_id_map)
     title_of = _title_of(data_handler.movies)
-    for (slot, _), row in zip(known, _ranked(idx, score)):
-        out[slot] = [{'movie_id': id_movie[i + num_users], 'title': title_of[id_movie[i + num_users]], 'score': s}
-                     for i, s in row]
+
+    def movie(i: int) -> Dict[str, Any]:
+        return {'movie_id': id_movie[i + num_users], 'title': title_of[id_movie[i + num_users]]}
+
+    if why is None:
+        for (slot, _), row in zip(known, _ranked(idx, score)):
+            out[slot] = [dict(movie(i), score=s) for i, s in row]
+        return out
+    idx, score, widx, wval = idx.tolist(), score.tolist(), why.idx.tolist(), why.value.tolist()
+    for q, (slot, _) in enumerate(known):
+        out[slot] = [dict(movie(i), score=s, because=[dict(movie(b), similarity=v) for b, v in zip(bi, bv) if b >= 0])
+                     for i, s, bi, bv in zip(idx[q], score[q], widx[q], wval[q]) if i >= 0]
     return out
 
 
@@ -160,6 +185,11 @@ if __name__ == '__main__':
     ei = train_data.edge_index
     seen_items = ei[1, ei[0] == handler.user_id_map[uid]] - handler.num_users
     result = recommend_from_user(model, uid, handler, seen_items)
+    why = recommend_for_users(model, [uid], handler, k=TOP_N, train_edge_index=ei, explain=3)[0]
+    because = {rec['title']: rec['because'] for rec in why}
     print(f"Top 10 Recommendations for user {uid}:")
     for rank, rec in enumerate(result['recommendations'], 1):
         print(f"{rank}. {rec['title']} (Score: {rec['score']:.4f})")
+        if because.get(rec['title']):
+            print("   because you watched: " + ", ".join(f"{b['title']} ({b['similarity']:.2f})"
+                                                          for b in because[rec['title']]))
