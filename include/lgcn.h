@@ -742,6 +742,41 @@ int lgcn_explain_topr(const int32_t* rec_idx, int64_t ld, int32_t k, int64_t Q,
                       int32_t* out_idx, float* out_val, int32_t* out_n, float* out_sum,
                       lgcn_stream_t stream);
 
+/* Fold-in (added under ABI 11, purely additive): the row of a node the model never saw, as one more
+ * propagation over its own edges gives it — per query the weighted sum of the table rows its
+ * history names, every trained row left as it is (csrc/lgcn_foldin.hip: one wave per history, eight
+ * for a long one).
+ *   history: CSR (hist_ptr int64[hist_rows + 1], hist_idx int32) with the row conventions of the
+ *     exclusion, truth and explain CSRs above: query q uses row hist_row[q] (row q when hist_row is
+ *     NULL); a row outside [0, hist_rows) is empty. Rows may be arbitrarily long; entries need be
+ *     neither sorted nor distinct, a repeated entry counts each time.
+ *   table: [M, d] f32 rows at a stride of ldt >= d floats (a column slice of a wider table is passed
+ *     as it is); isd (nullable): f32[M], one factor per table row, in practice 1 / sqrt(degree + 1);
+ *     hist_w (nullable): one f32 weight per CSR entry.
+ *   rule: entry e with i = hist_idx[e] is eligible when 0 <= i < M; other entries are skipped and
+ *     neither isd nor the table is read for them. n_q is the number of eligible entries, and
+ *       t_e[c] = (hist_w[e] * isd[i]) * table[i * ldt + c]      (f32 products as written; a factor
+ *                                                               whose pointer is NULL is left out)
+ *       out[q * ldo + c] = s_q * sum_e t_e[c],  c < d,  s_q = (float)(1.0 / sqrt((double)n_q)).
+ *     n_q == 0 gives a row of exact zeros. Columns [d, ldo) are not written. out_n[q] = n_q
+ *     (nullable pointer).
+ *   The f32 summation order is unspecified but a function of the history row's length and d alone:
+ *   the same history gives the same bits alone or in a batch, at any query position, through
+ *   hist_row or not, for any ldt or alignment of the table, and run to run. No atomics.
+ *   Histories of more than LGCN_FOLDIN_LONG entries are summed in chunks of LGCN_FOLDIN_CHUNK
+ *   entries by the eight waves of a workgroup.
+ * LGCN_E_ARG: a null required pointer (hist_w, hist_row, isd, out_n may be NULL), Q, M or hist_rows
+ * below 0, d < 1, ldt < d, ldo < d, ldt or Q above INT32_MAX. LGCN_E_UNSUPPORTED: d > LGCN_FOLDIN_MAX_D.
+ * Checked before any HIP call; Q == 0 returns LGCN_OK without a launch. Allocates nothing, reads
+ * nothing back, does not synchronise, needs no workspace. */
+#define LGCN_FOLDIN_MAX_D 256   /* columns of a table row */
+#define LGCN_FOLDIN_LONG 512    /* history entries above which eight waves share a history */
+#define LGCN_FOLDIN_CHUNK 512   /* entries of one wave's chunk of a long history */
+int lgcn_foldin_rows(const int64_t* hist_ptr, const int32_t* hist_idx, const float* hist_w,
+                     const int64_t* hist_row, int64_t hist_rows, int64_t Q,
+                     const float* table, int64_t M, int32_t d, int64_t ldt, const float* isd,
+                     float* out, int64_t ldo, int32_t* out_n, lgcn_stream_t stream);
+
 /* Host-only (no GPU): `draws` consecutive numpy legacy np.random.choice(n, size, replace=False)
  * calls (reference utils/train_test.py:187) on the MT19937 state (key[624], *pos) of
  * np.random.get_state(), written to out[draws*size]; key/pos are advanced exactly as numpy would

@@ -4,6 +4,9 @@ over every user with held-out items, on the HIP path of lgcn_amd.metrics.
 
     from utils.ranking_eval import evaluate_ranking
     evaluate_ranking(model, train_data.edge_index, test_data.edge_index, 'cuda', ks=(10, 20))
+
+evaluate_fold_in does the same for users the model never saw: their support items are folded in
+(lgcn_amd.foldin) and left out, their held-out items are the truth.
 """
 import torch
 
@@ -37,3 +40,36 @@ def evaluate_ranking(model: torch.nn.Module, train_edge_index: torch.Tensor, hel
         else:
             user_emb, item_emb = model(train_edge_index)
         return metrics.evaluate_ranking(user_emb, item_emb, truth, ks=ks, seen=seen, diversity=diversity, pool=pool)
+
+
+def evaluate_fold_in(model: torch.nn.Module, train_edge_index: torch.Tensor, support, heldout, device, ks=(20,),
+                     embeddings: str = "raw", diversity=None, pool=None) -> dict:
+    """How well the model serves users it never saw: ``support`` and ``heldout`` are CSRs
+    (ptr int64 [Q + 1], idx int32, 0-based item indices) over the same Q unseen users. Each user's
+    support items are folded in (lgcn_amd.foldin.fold_in, item degrees from ``train_edge_index``) and
+    left out of the ranking, the held-out items are the truth, and lgcn_amd.metrics.summarize's dict
+    comes back through lgcn_amd.metrics.evaluate_ranking.
+    embeddings="raw" folds against and ranks the raw item rows, what
+    utils.recommend.recommend_for_histories serves; "propagated" folds against
+    lgcn_amd.foldin.layer_tables' S_item and ranks model(train_edge_index)'s item rows.
+    diversity / pool: evaluate_ranking's."""
+    if embeddings not in ("raw", "propagated"):
+        raise ValueError(f"evaluate_fold_in: embeddings must be 'raw' or 'propagated', got {embeddings!r}")
+    from lgcn_amd import foldin, metrics
+    from lgcn_amd.recommend import seen_csr
+
+    model.eval()
+    U, I = model.num_users, model.num_items
+    with torch.no_grad():
+        train_edge_index = train_edge_index.to(device)
+        by_item = seen_csr(train_edge_index, U, I, by="item")
+        degree = by_item[0][1:] - by_item[0][:-1]
+        if embeddings == "raw":
+            table = item_emb = model.get_embeddings(item_indices=torch.arange(I, device=device))[1]
+        else:
+            item_emb = model(train_edge_index)[1]
+            table = foldin.layer_tables(model.user_embedding.weight, model.item_embedding.weight,
+                                        model.plan_for(train_edge_index), model.num_layers)[1]
+        support = (support[0].to(device), support[1].to(device))
+        rows = foldin.fold_in(support, table, count=degree).rows
+        return metrics.evaluate_ranking(rows, item_emb, heldout, ks=ks, seen=support, diversity=diversity, pool=pool)

@@ -10,7 +10,9 @@ lgcn_amd.recommend.topk_rows call with a one-row exclusion CSR ranks on the devi
 come in ascending index order. ``recommend_for_users`` serves a batch of users in one call, with
 ``diversity=`` a list re-ranked for diversity (greedy MMR over a relevance pool, on the device) and
 with ``explain=r`` every movie carrying the r movies of the user's history that point at it most
-strongly ('because', lgcn_amd.explain on the device).
+strongly ('because', lgcn_amd.explain on the device). ``recommend_for_histories`` serves people who
+were not in the training graph from the movies they name (fold-in, lgcn_amd.foldin on the device;
+``python utils/recommend.py --movies 1,296,318``).
 Not carried over: the plotting (``visualizations``) and the import-time seeding (nothing here draws
 random numbers). Unknown ids are answered without touching the GPU; everything else needs the model
 on a ROCm device (lgcn_amd._ffi.LgcnError otherwise, there is no CPU fallback).
@@ -29,6 +31,7 @@ if __name__ == '__main__':  # run as a script: the package root (this file's par
     sys.path.insert(0, os.path.abspath(os.path.join(os.path.dirname(os.path.abspath(__file__)), '..')))
 
 from lgcn_amd import explain as _explain
+from lgcn_amd import foldin as _foldin
 from lgcn_amd import recommend as _rec
 
 TOP_N = 10  # the reference's list length
@@ -169,6 +172,98 @@ def recommend_for_users(model: torch.nn.Module, user_ids: Sequence[int], data_ha
     return out
 
 
+def recommend_for_histories(model: torch.nn.Module, histories: Sequence[Sequence[int]], data_handler: Any, k: int = 10,
+                            exclude_history: bool = True, train_edge_index: Optional[torch.Tensor] = None,
+                            embeddings: str = "raw", weights: Optional[Sequence[Sequence[float]]] = None,
+                            diversity: Optional[float] = None, pool: Optional[int] = None,
+                            explain: Optional[int] = None
+                            ) -> List[Union[Dict[str, str], List[Dict[str, Any]]]]:
+    """Lists for people the model never saw — someone who has just rated a few films, an anonymous
+    session: one entry per history of ``histories`` (each a sequence of MovieLens movie ids), the k
+    best movies as recommend_for_users' dictionaries [{'movie_id', 'title', 'score'}], or
+    {'error': 'No known movie IDs'} where no id of the history is a movie of the handler. Unknown ids
+    are dropped and an id named twice counts once (a graph holds one edge per pair).
+    Each history is folded in on the device (lgcn_amd.foldin): the row one more propagation over the
+    history's edges would give the new user, every trained row left as it is — the sum of the
+    history's item rows, each over sqrt(n * (deg + 1)), n the history's known movies and deg the
+    movie's users in ``train_edge_index`` (default ``data_handler.edge_index``). ``weights``: one
+    sequence per history, one float per id (a rating, say), None for 1.
+    embeddings="raw" folds against and ranks the raw item rows, as every list of this module;
+    "propagated" folds against lgcn_amd.foldin.layer_tables' S_item and ranks
+    model(train_edge_index)'s item rows, which gives the new user the row the K-layer model would.
+    ``exclude_history`` leaves the history's movies out of the list. ``diversity`` / ``pool`` /
+    ``explain`` are recommend_for_users'; the 'because' movies come from the supplied history
+    (lgcn_amd.explain.explain_rows). All histories are served by one fold-in and one ranking call;
+    if no history has a known id the answer comes without touching the model or the GPU."""
+    if embeddings not in ("raw", "propagated"):
+        raise ValueError(f"recommend_for_histories: embeddings must be 'raw' or 'propagated', got {embeddings!r}")
+    if diversity is None and pool is not None:
+        raise ValueError("recommend_for_histories: pool is the re-rank's pool and needs diversity")
+    if explain is not None:
+        explain = int(explain)
+        if explain < 1 or explain > _explain.MAX_R:
+            raise ValueError(f"recommend_for_histories: explain={explain} outside [1, {_explain.MAX_R}]")
+    if weights is not None and len(weights) != len(histories):
+        raise ValueError(f"recommend_for_histories: {len(weights)} weight lists for {len(histories)} histories")
+    user_id_map, movie_id_map = data_handler.user_id_map, data_handler.movie_id_map
+    num_users, num_items = len(user_id_map), len(movie_id_map)
+    out: list = [{'error': 'No known movie IDs'} for _ in histories]
+    slots, rows, row_w = [], [], []
+    for slot, hist in enumerate(histories):
+        w = [1.0] * len(hist) if weights is None else list(weights[slot])
+        if len(w) != len(hist):
+            raise ValueError(f"recommend_for_histories: history {slot} has {len(hist)} ids and {len(w)} weights")
+        known: Dict[int, float] = {}
+        for m, x in zip(hist, w):
+            if m in movie_id_map:
+                known.setdefault(movie_id_map[m] - num_users, float(x))
+        if known:
+            slots.append(slot)
+            rows.append(sorted(known))  # ascending and distinct: the row also serves as exclusion and explain CSR
+            row_w.append([known[i] for i in rows[-1]])
+    if not slots:
+        return out
+    dev = model.user_embedding.weight.device
+    ptr = torch.tensor([0] + [len(r) for r in rows], dtype=torch.int64).cumsum(0).to(dev)
+    hidx = torch.tensor([i for r in rows for i in r], dtype=torch.int32, device=dev)
+    hw = None if weights is None else torch.tensor([x for r in row_w for x in r], dtype=torch.float32, device=dev)
+    history = (ptr, hidx)
+    ei = (data_handler.edge_index if train_edge_index is None else train_edge_index).to(dev)
+    by_item = _rec.seen_csr(ei, num_users, num_items, by="item")
+    degree = by_item[0][1:] - by_item[0][:-1]
+    with torch.no_grad():
+        if embeddings == "raw":
+            item_emb = model.get_embeddings(item_indices=torch.arange(num_items, device=dev))[1]
+            table = item_emb
+        else:
+            item_emb = model(ei)[1]
+            table = _foldin.layer_tables(model.user_embedding.weight, model.item_embedding.weight, model.plan_for(ei),
+                                         model.num_layers)[1]
+        queries = _foldin.fold_in(history, table, count=degree, weights=hw).rows
+        excl = history if exclude_history else None
+        if diversity is None:
+            idx, score = _rec.topk_rows(queries, torch.arange(len(slots)), item_emb, k, excl=excl)
+        else:
+            idx, score = _rec.topk_rows_diverse(queries, torch.arange(len(slots)), item_emb, k, diversity,
+                                                pool=pool, excl=excl)[:2]
+        why = None if explain is None else _explain.explain_rows(idx, history, item_emb, r=explain)
+    id_movie = _id_map(data_handler, "id_movie_map", movie_id_map)
+    title_of = _title_of(data_handler.movies)
+
+    def movie(i: int) -> Dict[str, Any]:
+        return {'movie_id': id_movie[i + num_users], 'title': title_of[id_movie[i + num_users]]}
+
+    if why is None:
+        for slot, row in zip(slots, _ranked(idx, score)):
+            out[slot] = [dict(movie(i), score=s) for i, s in row]
+        return out
+    idx, score, widx, wval = idx.tolist(), score.tolist(), why.idx.tolist(), why.value.tolist()
+    for q, slot in enumerate(slots):
+        out[slot] = [dict(movie(i), score=s, because=[dict(movie(b), similarity=v) for b, v in zip(bi, bv) if b >= 0])
+                     for i, s, bi, bv in zip(idx[q], score[q], widx[q], wval[q]) if i >= 0]
+    return out
+
+
 if __name__ == '__main__':
     from data.dataset_handler import MovieLensDataHandler
     from models.light_gcn import LightGCN
@@ -178,6 +273,18 @@ if __name__ == '__main__':
     if os.path.exists('best_model.pth'):
         model.load_state_dict(torch.load('best_model.pth', map_location='cuda'))
     model.eval()
+    if len(sys.argv) > 2 and sys.argv[1] == '--movies':  # someone the model never saw: --movies 1,296,318
+        watched = [int(m) for m in sys.argv[2].split(',') if m.strip()]
+        served = recommend_for_histories(model, [watched], handler, k=TOP_N, explain=3)[0]
+        if isinstance(served, dict):
+            sys.exit(served['error'])
+        print(f"Top 10 Recommendations for someone who watched {', '.join(map(str, watched))}:")
+        for rank, rec in enumerate(served, 1):
+            print(f"{rank}. {rec['title']} (Score: {rec['score']:.4f})")
+            if rec['because']:
+                print("   because you watched: " + ", ".join(f"{b['title']} ({b['similarity']:.2f})"
+                                                              for b in rec['because']))
+        sys.exit(0)
     uid = int(sys.argv[1]) if len(sys.argv) > 1 else next(iter(handler.user_id_map))
     if uid not in handler.user_id_map:
         sys.exit(recommend_from_user(model, uid, handler)['error'])
