@@ -393,7 +393,7 @@ int lgcn_copy_scale(const float* x_lo, const float* x_hi, int64_t x_split, int64
  * F: propagated table (split; user u at row u, item i at row U+i), W: layer-0 table (same).
  *   lgcn_bpr_fused writes, per triplet, dF rows cf[b], cf[B+b], cf[2B+b] (d loss / d F rows of
  *   u, p, n), reg-gradient rows cw[...] (d loss / d W rows) and terms[b] = softplus term,
- *   terms[B+b] = sum of squares of the three W rows. d in {16,32,64,128,256,512}.
+ *   terms[B+b] = sum of squares of the three W rows. d in {8,16,32,64,128,256,512}.
  *   touched (device uint8[N], nullable): rows with touched[r] == 0 were not propagated (a sparse
  *   batch plan) and their F row is (W[r] / div) * mul — LightGCN's output for a row no batch edge
  *   reaches (every layer adds an exact 0).
@@ -402,7 +402,7 @@ int lgcn_copy_scale(const float* x_lo, const float* x_hi, int64_t x_split, int64
  *   the deterministic scatter of those rows, with rowptr/perm from lgcn_csr_build over the 3B keys
  *   (u, U+p, U+n). add == 0 writes every row as (sum * mul) / div (0 where empty) — with the
  *   LightGCN backward scale this is the seed g of the backward; add != 0 only adds (sum * mul) / div
- *   to rows with contributions. */
+ *   to rows with contributions. d in {8,16,32,64,128,256,512}, as lgcn_bpr_fused. */
 /* cw may be NULL: the reg rows are then not materialised (lgcn_reg_rows_add and the scatters'
  * reg sources form their sums from W). */
 int lgcn_bpr_fused(const float* f_lo, const float* f_hi, int64_t f_split,
@@ -417,7 +417,8 @@ int lgcn_bpr_fused(const float* f_lo, const float* f_hi, int64_t f_split,
  *   (the caller all-reduces sums over the column groups)
  *   phase 2: reads the six full sums and writes cf / cw / terms as lgcn_bpr_fused does, for this
  *            rank's columns; the reg scale uses d_full (cw rows = coeff * 2 / (B * d_full) * W).
- * d in {8, 16, ..., 512}. Replaces the same reference code as lgcn_bpr_fused. */
+ * d in {8,16,32,64,128,256,512} (d_full >= d, any size). Replaces the same reference code as
+ * lgcn_bpr_fused. */
 int lgcn_bpr_fused_cols(const float* f_lo, const float* f_hi, int64_t f_split, const float* w_lo, const float* w_hi,
                         int64_t w_split, int64_t U, const int64_t* u, const int64_t* p, const int64_t* n, int64_t B,
                         int32_t d, int32_t d_full, const uint8_t* touched, float div, float mul, float coeff, float* sums,

@@ -1061,7 +1061,7 @@ int lgcn_segment_rows(const int64_t* rowptr, const int32_t* perm, const float* C
         case 128: return launch_seg<32, 1>(rowptr, perm, C, N, d, out_lo, out_hi, split, add, mul, div, s);
         case 256: return launch_seg<64, 1>(rowptr, perm, C, N, d, out_lo, out_hi, split, add, mul, div, s);
         case 512: return launch_seg<64, 2>(rowptr, perm, C, N, d, out_lo, out_hi, split, add, mul, div, s);
-        default: return fail(LGCN_E_UNSUPPORTED, "lgcn_segment_rows: d=%d (supported 16..512, powers of two)", d);
+        default: return fail(LGCN_E_UNSUPPORTED, "lgcn_segment_rows: d=%d (supported 8..512, powers of two)", d);
     }
 }
 
