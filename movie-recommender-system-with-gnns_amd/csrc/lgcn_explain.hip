@@ -49,6 +49,7 @@
 // workgroup whose occupancy does not pay for seven idle waves. The two launches write disjoint
 // queries. No atomics, no waiting on other workgroups, nothing allocated, stream-ordered.
 #include "lgcn_common.h"
+#include "lgcn_ragged.h"
 
 #include <cmath>
 
@@ -63,22 +64,10 @@ constexpr int kExplainWaves = 8;                  // waves that share a long his
 constexpr int kExplainLong = 512;                 // history entries above which they do
 constexpr int kExplainMergeBytes = kExplainList * 8 + 4;  // a wave's list and sum of one slot, in LDS
 
-// order-preserving image of a contribution (NaN counts as -inf, -0 as +0)
-__device__ __forceinline__ uint32_t explain_value_key(float v) {
-    if (!(v == v)) v = -INFINITY;
-    if (v == 0.f) v = 0.f;
-    const uint32_t u = __float_as_uint(v);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-__device__ __forceinline__ float explain_key_value(uint32_t key) {
-    return __uint_as_float((key & 0x80000000u) ? (key ^ 0x80000000u) : ~key);
-}
-
-// value image | inverted item index (31 bits) | "the value is a number" (a NaN decodes as NaN again)
+// value image (NaN as -inf, -0 as +0) | inverted item index (31 bits) | "the value is a number" (a NaN decodes as NaN again)
 __device__ __forceinline__ unsigned long long explain_word(float v, int32_t i) {
     const uint32_t low = (0x7FFFFFFFu - static_cast<uint32_t>(i)) << 1 | (v == v ? 1u : 0u);
-    return static_cast<unsigned long long>(explain_value_key(v)) << 32 | low;
+    return static_cast<unsigned long long>(ordered_key_nan_last(v)) << 32 | low;
 }
 
 // keep the kExplainList largest words, descending (0 = empty)
@@ -90,18 +79,6 @@ __device__ __forceinline__ void explain_insert(unsigned long long (&L)[kExplainL
             w = w > L[p] ? L[p] : w;
             L[p] = hi;
         }
-    }
-}
-
-// [beg, end) of query q's history row in hist_idx (empty for a row outside the CSR)
-__device__ __forceinline__ void explain_range(int64_t q, const int64_t* __restrict__ hist_ptr,
-                                              const int64_t* __restrict__ hist_row, int64_t hist_rows, int64_t& beg,
-                                              int64_t& end) {
-    beg = end = 0;
-    const int64_t row = hist_row ? hist_row[q] : q;
-    if (row >= 0 && row < hist_rows) {
-        beg = hist_ptr[row];
-        end = hist_ptr[row + 1];
     }
 }
 
@@ -323,7 +300,7 @@ __device__ __forceinline__ void explain_query(char* smem, int64_t q, int64_t beg
                     n += w != 0ull;
                     if ((p & 3) == g) {  // the slot's four lanes share the stores
                         const uint32_t low = static_cast<uint32_t>(w);
-                        const float val = (low & 1u) ? explain_key_value(static_cast<uint32_t>(w >> 32)) : NAN;
+                        const float val = (low & 1u) ? ordered_value(static_cast<uint32_t>(w >> 32)) : NAN;
                         out_idx[base + p] = w ? static_cast<int32_t>(0x7FFFFFFFu - (low >> 1)) : -1;
                         out_val[base + p] = w ? val : -INFINITY;
                     }
@@ -346,7 +323,7 @@ __global__ __launch_bounds__(64) void k_explain_topr(
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int64_t q = blockIdx.x;
     int64_t beg, end;
-    explain_range(q, hist_ptr, hist_row, hist_rows, beg, end);
+    ragged_row(q, hist_ptr, hist_row, hist_rows, beg, end);
     if (end - beg > kExplainLong) return;  // k_explain_topr_long's
     explain_query<KS, 1>(smem, q, beg, end, rec_idx, ld, k, hist_idx, hist_w, Cn, M, D, r, out_idx, out_val, out_n,
                          out_sum);
@@ -363,7 +340,7 @@ __global__ __launch_bounds__(64 * kExplainWaves) void k_explain_topr_long(
         const int64_t q = static_cast<int64_t>(blockIdx.x) * kExplainWaves + i;
         if (q >= Q) break;
         int64_t beg, end;
-        explain_range(q, hist_ptr, hist_row, hist_rows, beg, end);
+        ragged_row(q, hist_ptr, hist_row, hist_rows, beg, end);
         if (end - beg > kExplainLong)
             explain_query<KS, kExplainWaves>(smem, q, beg, end, rec_idx, ld, k, hist_idx, hist_w, Cn, M, D, r, out_idx,
                                              out_val, out_n, out_sum);

@@ -37,6 +37,7 @@
 // history over several workgroups would need a workspace for their partial sums and a third launch;
 // DESIGN.md §15 has the measured share of the longest history.
 #include "lgcn_common.h"
+#include "lgcn_ragged.h"
 
 #include <cmath>
 
@@ -52,19 +53,6 @@ constexpr int kFoldinShort = 4;                  // histories (waves) per workgr
 
 static_assert(kFoldinChunk % 64 == 0, "a chunk starts on lane group 0 whatever the row width");
 static_assert(LGCN_FOLDIN_MAX_D == 256, "a row is at most 64 lanes of four columns");
-
-// [beg, end) of query q's history row in hist_idx (empty for a row outside the CSR)
-__device__ __forceinline__ void foldin_range(int64_t q, const int64_t* __restrict__ hist_ptr,
-                                             const int64_t* __restrict__ hist_row, int64_t hist_rows, int64_t& beg,
-                                             int64_t& end) {
-    beg = end = 0;
-    const int64_t row = hist_row ? hist_row[q] : q;
-    if (row >= 0 && row < hist_rows) {
-        beg = hist_ptr[row];
-        end = hist_ptr[row + 1];
-        if (end < beg) end = beg;
-    }
-}
 
 struct FoldinTable {
     const float* table;
@@ -200,7 +188,7 @@ __global__ __launch_bounds__(64 * kFoldinShort) void k_foldin_rows(
     const int64_t q = static_cast<int64_t>(blockIdx.x) * kFoldinShort + (threadIdx.x >> 6);
     if (q >= Q) return;  // wave-uniform, and no barrier follows
     int64_t beg, end;
-    foldin_range(q, hist_ptr, hist_row, hist_rows, beg, end);
+    ragged_row(q, hist_ptr, hist_row, hist_rows, beg, end);
     if (end - beg > kFoldinLong) return;  // k_foldin_rows_long's
     const int p = lane & (P - 1), g = lane >> shift;
     float acc[4] = {0.f, 0.f, 0.f, 0.f};
@@ -223,7 +211,7 @@ __global__ __launch_bounds__(64 * kFoldinWaves) void k_foldin_rows_long(
         const int64_t q = static_cast<int64_t>(blockIdx.x) * kFoldinWaves + i;
         if (q >= Q) break;
         int64_t beg, end;
-        foldin_range(q, hist_ptr, hist_row, hist_rows, beg, end);
+        ragged_row(q, hist_ptr, hist_row, hist_rows, beg, end);
         if (end - beg <= kFoldinLong) continue;
         float acc[4] = {0.f, 0.f, 0.f, 0.f};
         int32_t cnt = 0;

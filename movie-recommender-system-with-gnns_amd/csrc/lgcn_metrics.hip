@@ -3,8 +3,8 @@
 //
 //   k_rank_metrics   one wave per query, four queries per 256-thread workgroup. The wave walks the
 //                    query's k ranks 64 at a time: each lane loads its candidate index (coalesced)
-//                    and binary-searches the query's sorted truth row (the search k_select_ranked
-//                    runs on its exclusion row); a ballot gives the step's 64-bit hit mask. Per
+//                    and binary-searches the query's sorted truth row (sorted_contains, as
+//                    k_select_ranked does on its exclusion row); a ballot gives the step's 64-bit hit mask. Per
 //                    cutoff the hit count is a popcount of the mask under "ranks below the
 //                    cutoff" and the lane adds its discount 1 / log2(rank + 2) to a float64
 //                    partial. One butterfly reduction at the end, lane 0 stores.
@@ -14,6 +14,7 @@
 // workgroups. The DCG is formed and summed in float64 and rounded to float32 once, on store: the
 // stored value is within one float32 ulp of the exact sum whatever the reduction order.
 #include "lgcn_common.h"
+#include "lgcn_ragged.h"
 
 namespace lgcn {
 
@@ -34,15 +35,10 @@ __global__ __launch_bounds__(kBlock) void k_rank_metrics(
     const int64_t q = static_cast<int64_t>(blockIdx.x) * kMetricWaves + (threadIdx.x >> 6);
     if (q >= Q) return;  // whole waves leave; nothing below synchronises across waves
     // this query's truth row (a row outside [0, truth_rows) is an empty set)
-    const int32_t* tr = truth_idx;
-    int64_t tn = 0;
-    const int64_t row = truth_row ? truth_row[q] : q;
-    if (row >= 0 && row < truth_rows) {
-        const int64_t beg = truth_ptr[row];
-        tn = truth_ptr[row + 1] - beg;
-        tr = truth_idx + beg;
-        if (tn < 0) tn = 0;
-    }
+    int64_t tb, te;
+    ragged_row(q, truth_ptr, truth_row, truth_rows, tb, te);
+    const int32_t* tr = truth_idx + tb;
+    const int64_t tn = te - tb;
     const int32_t* ranked = ranked_idx + q * ld;
     int32_t hits[kMetricCutoffs];
     double dcg[kMetricCutoffs];
@@ -58,15 +54,7 @@ __global__ __launch_bounds__(kBlock) void k_rank_metrics(
             bool hit = false;
             if (r < k) {
                 const int32_t cand = ranked[r];
-                if (cand >= 0) {  // the -1 tail of a short list is never a hit
-                    int64_t lo = 0, hi = tn;
-                    while (lo < hi) {
-                        const int64_t mid = (lo + hi) >> 1;
-                        if (tr[mid] < cand) lo = mid + 1;
-                        else hi = mid;
-                    }
-                    hit = lo < tn && tr[lo] == cand;
-                }
+                if (cand >= 0) hit = sorted_contains(tr, tn, cand);  // the -1 tail of a short list is never a hit
             }
             const unsigned long long mask = __ballot(hit);
             if (mask == 0ull) continue;  // wave-uniform

@@ -28,6 +28,7 @@
 // reference) rank first, as torch.topk ranks NaN above every number.
 
 #include "lgcn_common.h"
+#include "lgcn_ragged.h"
 
 using namespace lgcn;
 
@@ -35,16 +36,11 @@ namespace {
 
 using f32x16 = __attribute__((ext_vector_type(16))) float;
 
-__device__ __forceinline__ uint32_t score_key(float s) {
-    if (s != s) return 0xFFFFFFFFu;
-    const uint32_t u = __float_as_uint(s);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
+// ordered_key with every NaN first (the highest key)
+__device__ __forceinline__ uint32_t score_key(float s) { return s != s ? 0xFFFFFFFFu : ordered_key(s); }
 
 // inverse of score_key (the NaN key maps back to a NaN)
-__device__ __forceinline__ float key_score(uint32_t k) {
-    return __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k);
-}
+__device__ __forceinline__ float key_score(uint32_t k) { return ordered_value(k); }
 
 // one 32-lane half-wave per row
 __global__ __launch_bounds__(kBlock) void k_normalize_rows(const float* __restrict__ x, const int64_t* __restrict__ idx,
@@ -398,32 +394,16 @@ __global__ __launch_bounds__(kSelBlock) void k_select_ranked(
     const uint32_t* keys = list_key + q * cap;
     const int32_t* idx = list_idx + q * cap;
     // this query's exclusion row (a row outside [0, excl_rows) excludes nothing)
-    const int32_t* ex = nullptr;
-    int64_t exn = 0;
-    if (excl_ptr) {
-        const int64_t row = excl_row ? excl_row[q] : q;
-        if (row >= 0 && row < excl_rows) {
-            const int64_t beg = excl_ptr[row];
-            exn = excl_ptr[row + 1] - beg;
-            ex = excl_idx + beg;
-            if (exn < 0) exn = 0;
-        }
-    }
+    int64_t exb = 0, exe = 0;
+    if (excl_ptr) ragged_row(q, excl_ptr, excl_row, excl_rows, exb, exe);
+    const int32_t* ex = excl_idx + exb;
+    const int64_t exn = exe - exb;
     // 1. eligibility bits, 64 entries per wave step
     int32_t mine = 0;
     for (int32_t base = wv * 64; base < n; base += kSelBlock) {
         const int32_t e = base + lane;
         bool ok = e < n;
-        if (ok && exn > 0) {
-            const int32_t c = idx[e];
-            int64_t lo = 0, hi = exn;
-            while (lo < hi) {
-                const int64_t mid = (lo + hi) >> 1;
-                if (ex[mid] < c) lo = mid + 1;
-                else hi = mid;
-            }
-            ok = !(lo < exn && ex[lo] == c);
-        }
+        if (ok && exn > 0) ok = !sorted_contains(ex, exn, idx[e]);
         const unsigned long long m = __ballot(ok);
         if (lane == 0) {
             elig[base >> 6] = m;

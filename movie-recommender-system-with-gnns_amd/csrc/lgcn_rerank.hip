@@ -28,6 +28,7 @@
 // above 64 KiB of LDS needs the kernel's dynamic-LDS attribute raised; the entry point does that
 // (a host-side call, no synchronisation) before such a launch.
 #include "lgcn_common.h"
+#include "lgcn_ragged.h"
 
 #include <cmath>
 
@@ -37,14 +38,6 @@ namespace lgcn {
 
 constexpr int kMmrMaxSlots = LGCN_MMR_MAX_POOL / 64;
 constexpr int kMmrRowPad = 4;  // floats between LDS rows beyond D (one 16-byte access width)
-
-// order-preserving image of a value (NaN counts as -inf, -0 as +0): a > b  <=>  image(a) > image(b)
-__device__ __forceinline__ uint32_t mmr_value_key(float v) {
-    if (!(v == v)) v = -INFINITY;
-    if (v == 0.f) v = 0.f;
-    const uint32_t u = __float_as_uint(v);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
 
 template <int SLOTS>
 __global__ __launch_bounds__(64) void k_rerank_mmr(
@@ -127,7 +120,7 @@ __global__ __launch_bounds__(64) void k_rerank_mmr(
                 const float a = keep * rel[j];
                 const float b = delta * mx[j];
                 const float v = a - b;
-                const unsigned long long w = static_cast<unsigned long long>(mmr_value_key(v)) << 32 |
+                const unsigned long long w = static_cast<unsigned long long>(ordered_key_nan_last(v)) << 32 |
                                              (0xFFFFFFFFu - static_cast<uint32_t>(j * 64 + lane));
                 best = w > best ? w : best;
             }

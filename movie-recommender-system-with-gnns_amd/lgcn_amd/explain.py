@@ -19,9 +19,7 @@ from typing import NamedTuple
 
 import torch
 
-from . import _ffi
-from .recall import _normalize_into
-from .recommend import _width
+from . import _ffi, _serving
 
 MAX_K = _ffi.EXPLAIN_MAX_K  # recommended slots per query
 MAX_R = _ffi.EXPLAIN_MAX_R  # reasons per slot
@@ -35,23 +33,6 @@ class Explained(NamedTuple):
     total: torch.Tensor  # f32 [Q, k]: the sum of the contributions of ALL eligible history entries
 
 
-def _history_args(history, Q: int):
-    """(ptr, idx, rows | None) of a history argument, checked as recommend._excl_args checks excl."""
-    if history is None or len(history) not in (2, 3):
-        raise ValueError("explain: history is (ptr, idx) or (ptr, idx, rows)")
-    ptr, idx = history[0], history[1]
-    rows = history[2] if len(history) == 3 else None
-    if ptr.dtype != torch.int64 or idx.dtype != torch.int32 or ptr.dim() != 1 or idx.dim() != 1 or ptr.numel() < 1:
-        raise TypeError("explain: history needs ptr int64 [R + 1] and idx int32 (see recommend.seen_csr)")
-    if rows is not None:
-        rows = torch.as_tensor(rows).view(-1)
-        if rows.numel() != Q:
-            raise ValueError(f"explain: history rows has {rows.numel()} entries for {Q} queries")
-    elif ptr.numel() - 1 < Q:
-        raise ValueError(f"explain: history has {ptr.numel() - 1} rows for {Q} queries (pass the row of each query)")
-    return ptr, idx, rows
-
-
 def explain_rows(rec_idx: torch.Tensor, history, candidates: torch.Tensor, r: int = 3, weights=None,
                  normalized: bool = False) -> Explained:
     """For every slot of rec_idx [Q, k] (int32 or int64; topk_rows' or rerank_mmr's idx, possibly a
@@ -60,8 +41,8 @@ def explain_rows(rec_idx: torch.Tensor, history, candidates: torch.Tensor, r: in
     n, total), lgcn_explain_topr's rule (module docstring).
 
     history: the CSR (ptr, idx) of recommend.seen_csr — row q belongs to query q — or
-    (ptr, idx, rows) with rows[q] naming the CSR row of query q; a row outside the CSR is an empty
-    history, entries outside [0, M) are skipped. candidates [M, d] f32: normalised once here; with
+    (ptr, idx, rows) with rows[q] naming the CSR row of query q (checked by _serving.csr_arg); a row
+    outside the CSR is an empty history, entries outside [0, M) are skipped. candidates [M, d] f32: normalised once here; with
     normalized=True taken as they are and only zero-padded to the kernel's width. weights: f32, one
     per CSR entry, on the device (None: 1).
     Limits: 1 <= k <= MAX_K, 1 <= r <= MAX_R, d <= 256 (ValueError before anything is loaded). The
@@ -69,8 +50,7 @@ def explain_rows(rec_idx: torch.Tensor, history, candidates: torch.Tensor, r: in
     r = int(r)
     if rec_idx.dim() != 2:
         raise ValueError("explain: rec_idx must be [Q, k]")
-    if rec_idx.dtype not in (torch.int32, torch.int64):
-        raise TypeError(f"explain: rec_idx must be int32 or int64, got {rec_idx.dtype}")
+    _serving.require_index_dtype("explain", "rec_idx", rec_idx)
     if candidates.dim() != 2 or candidates.dtype != torch.float32:
         raise TypeError("explain: candidates must be 2-D float32")
     Q, k = rec_idx.shape
@@ -79,13 +59,9 @@ def explain_rows(rec_idx: torch.Tensor, history, candidates: torch.Tensor, r: in
         raise ValueError(f"explain: k={k} recommended slots outside [1, {MAX_K}]")
     if r < 1 or r > MAX_R:
         raise ValueError(f"explain: r={r} outside [1, {MAX_R}]")
-    D = _width(d)
-    ptr, hidx, hrow = _history_args(history, Q)
-    if weights is not None:
-        if weights.dtype != torch.float32 or weights.dim() != 1:
-            raise TypeError("explain: weights must be 1-D float32")
-        if weights.numel() != hidx.numel():
-            raise ValueError(f"explain: {weights.numel()} weights for {hidx.numel()} history entries")
+    D = _serving.width("explain", d)
+    ptr, hidx, hrow, _ = _serving.csr_arg("explain", "history", history, Q)
+    _serving.check_weights("explain", weights, hidx.numel())
     lib = _ffi.load()
     for t in (rec_idx, candidates) + (() if weights is None else (weights,)):
         _ffi.require_device(t, "explain")
@@ -102,22 +78,9 @@ def explain_rows(rec_idx: torch.Tensor, history, candidates: torch.Tensor, r: in
         hrow = hrow.to(device=dev, dtype=torch.int64).contiguous()
     if weights is not None:
         weights = weights.detach().contiguous()
-    if index_dtype == torch.int64:  # a value outside int32 cannot be a candidate: an empty slot, not wrapped
-        fits = (rec_idx >= 0) & (rec_idx <= torch.iinfo(torch.int32).max)
-        rec_idx = torch.where(fits, rec_idx, -1).to(torch.int32)
-    if not (rec_idx.stride(1) == 1 and rec_idx.stride(0) >= k):
-        rec_idx = rec_idx.contiguous()
-    ld = rec_idx.stride(0) if Q > 1 else k  # a single row's stride means nothing
+    rec_idx, ld = _serving.index_list(rec_idx)
     s = _ffi.stream_of(dev)
-    candidates = candidates.detach()
-    if normalized and d == D and candidates.is_contiguous() and candidates.data_ptr() % 16 == 0 and M > 0:
-        Cn = candidates
-    else:
-        Cn = torch.zeros((max(M, 1), D), dtype=torch.float32, device=dev)
-        if normalized:
-            Cn[:M, :d] = candidates
-        else:
-            _normalize_into(lib, candidates, None, M, Cn.data_ptr(), D, M, s)
+    Cn = _serving.unit_rows(lib, candidates, D, normalized, s)
     _ffi.check(lib.lgcn_explain_topr(rec_idx.data_ptr(), ld, k, Q, ptr.data_ptr(), hidx.data_ptr(), _ffi.ptr(weights),
                                      _ffi.ptr(hrow), ptr.numel() - 1, Cn.data_ptr(), M, D, r, out_idx.data_ptr(),
                                      out_val.data_ptr(), out_n.data_ptr(), out_sum.data_ptr(), s), "lgcn_explain_topr")

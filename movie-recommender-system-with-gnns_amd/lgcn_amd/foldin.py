@@ -26,7 +26,7 @@ from typing import NamedTuple
 import numpy as np
 import torch
 
-from . import _ffi
+from . import _ffi, _serving
 
 MAX_D = _ffi.FOLDIN_MAX_D  # columns of a table row
 LONG = _ffi.FOLDIN_LONG    # history entries above which eight waves share a history
@@ -37,24 +37,6 @@ class FoldedIn(NamedTuple):
     """lgcn_foldin_rows' outputs for Q histories, on the device."""
     rows: torch.Tensor  # f32 [Q, d]: the folded-in rows, exact zeros for a history without eligible entries
     n: torch.Tensor     # int32 [Q]: eligible entries (those naming a table row) of each history
-
-
-def _history_args(history):
-    """(ptr, idx, rows | None, Q) of a history argument, checked as explain._history_args checks it;
-    Q is the number of rows named, or of CSR rows when none are."""
-    if history is None or len(history) not in (2, 3):
-        raise ValueError("fold_in: history is (ptr, idx) or (ptr, idx, rows)")
-    ptr, idx = history[0], history[1]
-    rows = history[2] if len(history) == 3 else None
-    if not (torch.is_tensor(ptr) and torch.is_tensor(idx)) or ptr.dtype != torch.int64 or idx.dtype != torch.int32 \
-            or ptr.dim() != 1 or idx.dim() != 1 or ptr.numel() < 1:
-        raise TypeError("fold_in: history needs ptr int64 [R + 1] and idx int32 (see recommend.seen_csr)")
-    if rows is None:
-        return ptr, idx, None, ptr.numel() - 1
-    rows = torch.as_tensor(rows).view(-1)
-    if rows.dtype.is_floating_point or rows.dtype == torch.bool:
-        raise TypeError(f"fold_in: history rows must be integers, got {rows.dtype}")
-    return ptr, idx, rows, rows.numel()
 
 
 def inv_sqrt_degree(count: torch.Tensor, new_edge: bool = True) -> torch.Tensor:
@@ -76,13 +58,13 @@ def fold_in_rows(history, table: torch.Tensor, isd: torch.Tensor | None = None,
     counts each time, n_q = 0 gives a zero row.
 
     history: the CSR (ptr int64 [R + 1], idx int32) — one output row per CSR row — or
-    (ptr, idx, rows) with rows[q] naming the CSR row of output q; a row outside the CSR is an empty
-    history. table [M, d] f32 on the device, d <= MAX_D: a column slice or a row-strided view of a
-    wider tensor is read in place (only a view whose columns are not adjacent is copied). isd: f32
+    (ptr, idx, rows) with rows[q] naming the CSR row of output q (checked by _serving.csr_arg); a row
+    outside the CSR is an empty history. table [M, d] f32 on the device, d <= MAX_D: a column slice
+    or a row-strided view of a wider tensor is read in place (only a view whose columns are not adjacent is copied). isd: f32
     [M], one factor per table row (inv_sqrt_degree); weights: f32, one per CSR entry; None: 1.
     The same history gives the same bits alone or in a batch, at any position, and run to run.
     ValueError / TypeError for bad arguments before anything is loaded."""
-    ptr, hidx, hrow, Q = _history_args(history)
+    ptr, hidx, hrow, Q = _serving.csr_arg("fold_in", "history", history)
     if not torch.is_tensor(table) or table.dim() != 2 or table.dtype != torch.float32:
         raise TypeError("fold_in: table must be a 2-D float32 tensor")
     M, d = table.shape
@@ -93,11 +75,7 @@ def fold_in_rows(history, table: torch.Tensor, isd: torch.Tensor | None = None,
             raise TypeError("fold_in: isd must be 1-D float32")
         if isd.numel() != M:
             raise ValueError(f"fold_in: {isd.numel()} isd factors for {M} table rows")
-    if weights is not None:
-        if not torch.is_tensor(weights) or weights.dtype != torch.float32 or weights.dim() != 1:
-            raise TypeError("fold_in: weights must be 1-D float32")
-        if weights.numel() != hidx.numel():
-            raise ValueError(f"fold_in: {weights.numel()} weights for {hidx.numel()} history entries")
+    _serving.check_weights("fold_in", weights, hidx.numel())
     lib = _ffi.load()
     for t in (table,) + tuple(x for x in (isd, weights) if x is not None):
         _ffi.require_device(t, "fold_in")
@@ -109,10 +87,7 @@ def fold_in_rows(history, table: torch.Tensor, isd: torch.Tensor | None = None,
     ptr, hidx = ptr.to(dev).contiguous(), hidx.to(dev).contiguous()
     if hrow is not None:
         hrow = hrow.to(device=dev, dtype=torch.int64).contiguous()
-    table = table.detach()
-    if table.stride(1) != 1 or (M > 1 and table.stride(0) < d):
-        table = table.contiguous()
-    ldt = table.stride(0) if M > 1 else d  # a single row's stride means nothing
+    table, ldt = _serving.row_view(table.detach())
     isd = None if isd is None else isd.detach().contiguous()
     weights = None if weights is None else weights.detach().contiguous()
     _ffi.check(lib.lgcn_foldin_rows(ptr.data_ptr(), hidx.data_ptr(), _ffi.ptr(weights), _ffi.ptr(hrow), ptr.numel() - 1,

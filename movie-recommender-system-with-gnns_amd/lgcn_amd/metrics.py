@@ -26,7 +26,7 @@ from typing import NamedTuple
 
 import torch
 
-from . import _ffi, recommend
+from . import _ffi, _serving, recommend
 
 MAX_CUTOFFS = _ffi.METRICS_MAX_CUTOFFS
 METRICS = ("recall", "precision", "hit_rate", "ndcg", "mrr")
@@ -58,7 +58,8 @@ def rank_metrics(ranked_idx: torch.Tensor, truth, ks, rows=None) -> RankCounts:
     slots. An int64 value outside int32 cannot be a truth index and is taken as -1 (never a hit)
     rather than wrapped. Rows may be strided (a column slice of a wider tensor).
     truth: (ptr int64 [R + 1], idx int32) as recommend.seen_csr builds it; rows[q] names the truth
-    row of query q (row q when rows is None); a row outside [0, R) is an empty set.
+    row of query q (row q when rows is None); a row outside [0, R) is an empty set. Both are checked
+    by _serving.csr_arg.
     ks: cutoffs, any iterable of ints in [1, k]; sorted and deduplicated, at most MAX_CUTOFFS.
     The columns of the result follow the sorted cutoffs."""
     if ranked_idx.dim() != 2:
@@ -67,26 +68,17 @@ def rank_metrics(ranked_idx: torch.Tensor, truth, ks, rows=None) -> RankCounts:
     if k < 1 or k > _ffi.RANKED_MAX_K:
         raise ValueError(f"rank_metrics: k={k} outside [1, {_ffi.RANKED_MAX_K}]")
     cs = _cutoffs(ks, k)
+    _serving.require_index_dtype("rank_metrics", "ranked_idx", ranked_idx)
     if len(truth) != 2:
         raise ValueError("rank_metrics: truth is (ptr, idx)")
-    ptr, idx = truth
-    if ptr.dtype != torch.int64 or idx.dtype != torch.int32 or ptr.dim() != 1 or idx.dim() != 1 or ptr.numel() < 1:
-        raise TypeError("rank_metrics: truth needs ptr int64 [R + 1] and idx int32 (see recommend.seen_csr)")
-    if rows is not None:
-        rows = torch.as_tensor(rows).reshape(-1)
-        if rows.numel() != Q:
-            raise ValueError(f"rank_metrics: rows has {rows.numel()} entries for {Q} queries")
+    # a truth CSR may end before the queries do: those queries have empty rows
+    truth = tuple(truth) if rows is None else (*truth, rows)
+    ptr, idx, rows, _ = _serving.csr_arg("rank_metrics", "truth", truth, Q, short=True)
     lib = _ffi.load()
     for t in (ranked_idx, ptr, idx):
         _ffi.require_device(t, "rank_metrics")
     dev = ranked_idx.device
-    if ranked_idx.dtype != torch.int32:
-        if ranked_idx.dtype != torch.int64:
-            raise TypeError(f"rank_metrics: ranked_idx must be int32 or int64, got {ranked_idx.dtype}")
-        fits = (ranked_idx >= 0) & (ranked_idx <= torch.iinfo(torch.int32).max)
-        ranked_idx = torch.where(fits, ranked_idx, -1).to(torch.int32)  # no wrap-around, no host read
-    if ranked_idx.stride(1) != 1 or ranked_idx.stride(0) < k:
-        ranked_idx = ranked_idx.contiguous()
+    ranked_idx, ld = _serving.index_list(ranked_idx)
     ptr, idx = ptr.contiguous(), idx.contiguous()
     if idx.numel() == 0:  # every row is empty: the library still wants an address
         idx = torch.zeros(1, dtype=torch.int32, device=dev)
@@ -99,7 +91,6 @@ def rank_metrics(ranked_idx: torch.Tensor, truth, ks, rows=None) -> RankCounts:
     n_truth = torch.empty(Q, dtype=torch.int32, device=dev)
     if Q:
         cut = (ctypes.c_int32 * C)(*cs)
-        ld = ranked_idx.stride(0) if Q > 1 else k  # a single row's stride means nothing
         _ffi.check(lib.lgcn_rank_metrics(ranked_idx.data_ptr(), ld, k, Q, ptr.data_ptr(),
                                          idx.data_ptr(), _ffi.ptr(rows), ptr.numel() - 1, cut, C, hits.data_ptr(),
                                          dcg.data_ptr(), first.data_ptr(), n_truth.data_ptr(), _ffi.stream_of(dev)),

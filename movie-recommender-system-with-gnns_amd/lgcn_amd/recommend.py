@@ -30,7 +30,7 @@ from typing import NamedTuple
 
 import torch
 
-from . import _ffi
+from . import _ffi, _serving
 from .recall import _normalize_into
 
 # list workspace of one query block (8 bytes per list slot: key + index); follows recall.STL_BLOCK_BYTES
@@ -71,26 +71,16 @@ def seen_csr(edge_index: torch.Tensor, num_users: int, num_items: int, by: str =
 
 
 def _excl_args(excl, dev, Q: int):
-    """(ptr, idx, rows | None, R) of an exclusion argument, checked and on the device."""
+    """(ptr, idx, rows | None, R) of an exclusion argument, checked (_serving.csr_arg) and on the
+    device; all None / 0 when nothing is excluded."""
     if excl is None:
         return None, None, None, 0
-    if len(excl) not in (2, 3):
-        raise ValueError("recommend: excl is (ptr, idx) or (ptr, idx, rows)")
-    ptr, idx = excl[0], excl[1]
-    rows = excl[2] if len(excl) == 3 else None
-    if ptr.dtype != torch.int64 or idx.dtype != torch.int32 or ptr.dim() != 1 or idx.dim() != 1 or ptr.numel() < 1:
-        raise TypeError("recommend: excl needs ptr int64 [R + 1] and idx int32 (see seen_csr)")
-    ptr, idx = ptr.to(dev).contiguous(), idx.to(dev).contiguous()
-    R = ptr.numel() - 1
-    if rows is not None:
-        rows = torch.as_tensor(rows).to(device=dev, dtype=torch.int64).contiguous().view(-1)
-        if rows.numel() != Q:
-            raise ValueError(f"recommend: excl rows has {rows.numel()} entries for {Q} queries")
-    elif R < Q:
-        raise ValueError(f"recommend: excl has {R} rows for {Q} queries (pass the row of each query)")
+    ptr, idx, rows, _ = _serving.csr_arg("recommend", "excl", excl, Q)
     if idx.numel() == 0:  # nothing to exclude anywhere (and no device address to pass)
         return None, None, None, 0
-    return ptr, idx, rows, R
+    if rows is not None:
+        rows = rows.to(device=dev, dtype=torch.int64).contiguous()
+    return ptr.to(dev).contiguous(), idx.to(dev).contiguous(), rows, ptr.numel() - 1
 
 
 def topk_rows(queries: torch.Tensor, picked: torch.Tensor, candidates: torch.Tensor, k: int, excl=None,
@@ -231,16 +221,6 @@ def _diversity(diversity) -> float:
     return d
 
 
-def _width(d: int) -> int:
-    """lgcn_recall_width's D for rows of d columns, formed on the host (nothing is loaded)."""
-    if d < 1 or d > 256:
-        raise ValueError(f"recommend: rows of {d} columns (1 to 256 are supported)")
-    D = 8
-    while D < d:
-        D <<= 1
-    return D
-
-
 def rerank_mmr(pool_idx: torch.Tensor, pool_score: torch.Tensor, candidates: torch.Tensor, k: int, diversity: float,
                normalized: bool = False) -> Reranked:
     """Greedy Maximal Marginal Relevance over per-query pools, on the device (lgcn_rerank_mmr).
@@ -260,8 +240,7 @@ def rerank_mmr(pool_idx: torch.Tensor, pool_score: torch.Tensor, candidates: tor
     k, diversity = int(k), _diversity(diversity)
     if pool_idx.dim() != 2 or pool_score.shape != pool_idx.shape:
         raise ValueError("rerank_mmr: pool_idx and pool_score must both be [Q, N]")
-    if pool_idx.dtype not in (torch.int32, torch.int64):
-        raise TypeError(f"rerank_mmr: pool_idx must be int32 or int64, got {pool_idx.dtype}")
+    _serving.require_index_dtype("rerank_mmr", "pool_idx", pool_idx)
     if pool_score.dtype != torch.float32:
         raise TypeError(f"rerank_mmr: pool_score must be float32, got {pool_score.dtype}")
     if candidates.dim() != 2 or candidates.dtype != torch.float32:
@@ -272,7 +251,7 @@ def rerank_mmr(pool_idx: torch.Tensor, pool_score: torch.Tensor, candidates: tor
         raise ValueError(f"rerank_mmr: k={k} outside [1, N={N}]")
     if N > MMR_MAX_POOL:
         raise ValueError(f"rerank_mmr: a pool of {N} entries exceeds MMR_MAX_POOL={MMR_MAX_POOL}")
-    D = _width(d)
+    D = _serving.width("recommend", d)
     if N * D * 4 > MMR_MAX_LDS_BYTES:
         raise ValueError(f"rerank_mmr: {N} pool rows of width {D} take {N * D * 4} bytes, above "
                          f"MMR_MAX_LDS_BYTES={MMR_MAX_LDS_BYTES} (at most {MMR_MAX_LDS_BYTES // (4 * D)} rows)")
@@ -281,24 +260,12 @@ def rerank_mmr(pool_idx: torch.Tensor, pool_score: torch.Tensor, candidates: tor
         _ffi.require_device(t, "rerank_mmr")
     dev = pool_idx.device
     index_dtype = pool_idx.dtype
-    if index_dtype == torch.int64:  # a value outside int32 cannot be a candidate: skipped, not wrapped
-        fits = (pool_idx >= 0) & (pool_idx <= torch.iinfo(torch.int32).max)
-        pool_idx = torch.where(fits, pool_idx, -1).to(torch.int32)
+    pool_idx, ld = _serving.index_list(pool_idx)
     pool_score = pool_score.detach()
-    if not (pool_idx.stride(1) == 1 and pool_score.stride(1) == 1 and pool_idx.stride(0) >= N
-            and (Q <= 1 or pool_idx.stride(0) == pool_score.stride(0))):  # one leading dimension serves both
-        pool_idx, pool_score = pool_idx.contiguous(), pool_score.contiguous()
-    ld = pool_idx.stride(0) if Q > 1 else N  # a single row's stride means nothing
+    if pool_score.stride(1) != 1 or (Q > 1 and pool_score.stride(0) != ld):  # one leading dimension serves both
+        pool_idx, pool_score, ld = pool_idx.contiguous(), pool_score.contiguous(), N
     s = _ffi.stream_of(dev)
-    candidates = candidates.detach()
-    if normalized and d == D and candidates.is_contiguous() and candidates.data_ptr() % 16 == 0 and M > 0:
-        Cn = candidates
-    else:
-        Cn = torch.zeros((max(M, 1), D), dtype=torch.float32, device=dev)
-        if normalized:
-            Cn[:M, :d] = candidates
-        else:
-            _normalize_into(lib, candidates, None, M, Cn.data_ptr(), D, M, s)
+    Cn = _serving.unit_rows(lib, candidates, D, normalized, s)
     out_idx = torch.empty((Q, k), dtype=torch.int32, device=dev)
     out_score = torch.empty((Q, k), dtype=torch.float32, device=dev)
     out_pair = torch.empty((Q, k), dtype=torch.float32, device=dev)
@@ -324,7 +291,7 @@ def topk_rows_diverse(queries: torch.Tensor, picked: torch.Tensor, candidates: t
         raise ValueError(f"recommend: k={k} outside [1, {MMR_MAX_POOL}]")
     if queries.dim() != 2 or candidates.dim() != 2:
         raise ValueError("recommend: queries and candidates must be 2-D")
-    M, D = candidates.shape[0], _width(candidates.shape[1])
+    M, D = candidates.shape[0], _serving.width("recommend", candidates.shape[1])
     want = max(4 * k, 64) if pool is None else int(pool)
     limits = {"the candidate count M": M, "MMR_MAX_POOL": MMR_MAX_POOL,
               f"MMR_MAX_LDS_BYTES // (4 * D) at D={D}": MMR_MAX_LDS_BYTES // (4 * D)}

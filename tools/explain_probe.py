@@ -21,16 +21,9 @@ The last line is one JSON record: the timings, the ratio torch / explain, and th
 comes from a kernel trace in a run of its own
 (rocprofv3 --kernel-trace --stats -- python tools/explain_probe.py --reps 1).
 """
-import argparse
-import json
-import os
-import sys
-import time
-
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "movie-recommender-system-with-gnns_amd"))
+import _probe
 
 TORCH_BLOCK_BYTES = 1 << 30  # the padded gather of one block: B * L * D * 4
 
@@ -77,19 +70,13 @@ def torch_explain(buckets, ptr, idx, users, rec_idx, item_emb, r):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--reps", type=int, default=5)
-    ap.add_argument("--scale", type=float, default=1.0)
-    ap.add_argument("--dim", type=int, default=64)
+    ap = _probe.parser(reps=5)
     ap.add_argument("--k", type=int, default=10)
     ap.add_argument("--r", type=int, default=3)
-    ap.add_argument("--out", default=None)
     args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("explain_probe needs a ROCm device (a CPU timing says nothing here)")
+    dev = _probe.device("explain_probe")
     from lgcn_amd import explain, recommend, synth
 
-    dev = torch.device("cuda")
     g = synth.ml25m_shaped(seed=0, scale=args.scale)
     U, I = g.num_users, g.num_items
     seen = recommend.seen_csr(torch.from_numpy(g.edge_index).to(dev), U, I, by="user")
@@ -114,39 +101,17 @@ def main():
             "explain": lambda: explain.explain_items(item_emb, users, rec32, seen, r=r),
             "torch": lambda: torch_explain(buckets, ptr, sidx, users, rec64, item_emb, r),
             "longest": lambda: explain.explain_items(item_emb, heavy, rec32[heavy], seen, r=r)}
-
-    def timed(fn):
-        torch.cuda.synchronize()
-        t = time.perf_counter()
-        out = fn()
-        torch.cuda.synchronize()
-        return out, (time.perf_counter() - t) * 1e3
-
-    results, times = {}, {name: [] for name in arms}
-    for name, fn in arms.items():  # warm-up: code objects, allocator pools
-        results[name], _ = timed(fn)
-    for _ in range(args.reps):
-        for name, fn in arms.items():
-            _, ms = timed(fn)
-            times[name].append(ms)
-            print(f"{name}: {ms:.2f} ms", flush=True)
+    results, times = _probe.run_arms(arms, args.reps, 2)
     rec = dict(users=U, items=I, dim=args.dim, k=k, r=r, seen_entries=int(sidx.numel()),
                longest_history=int(length.max()), mean_history=round(float(length.float().mean()), 2), reps=args.reps)
-    for name, ts in times.items():
-        rec[f"{name}_ms"] = round(sorted(ts)[len(ts) // 2], 3)
-        rec[f"{name}_ms_all"] = [round(t, 3) for t in ts]
+    _probe.put_times(rec, times, 3)
     rec["torch_over_explain"] = round(rec["torch_ms"] / rec["explain_ms"], 3)
     rec["explain_cost_ms"] = round(rec["served_ms"] - rec["topk_ms"], 3)
     ours, theirs = results["explain"], results["torch"]
     rec["same_item_share"] = round(float((ours.idx.to(torch.int64) == theirs).float().mean()), 6)
     rec["served_equals_explain"] = bool(torch.equal(results["served"].idx, ours.idx))
     rec["filled_share"] = round(float((ours.idx >= 0).float().mean()), 6)
-    line = json.dumps(rec)
-    print(line, flush=True)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(line + "\n")
+    _probe.emit(rec, args.out)
 
 
 if __name__ == "__main__":

@@ -19,16 +19,9 @@ between the two arms relative to the row's largest entry, and whether two fold-i
 for bit. The kernels' own times come from a kernel trace in a run of its own
 (rocprofv3 --kernel-trace --stats -- python tools/foldin_probe.py --reps 1).
 """
-import argparse
-import json
-import os
-import sys
-import time
-
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "movie-recommender-system-with-gnns_amd"))
+import _probe
 
 
 def torch_foldin(ptr, idx, table, isd):
@@ -43,18 +36,12 @@ def torch_foldin(ptr, idx, table, isd):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--reps", type=int, default=5)
-    ap.add_argument("--scale", type=float, default=1.0)
-    ap.add_argument("--dim", type=int, default=64)
+    ap = _probe.parser(reps=5)
     ap.add_argument("--k", type=int, default=10)
-    ap.add_argument("--out", default=None)
     args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("foldin_probe needs a ROCm device (a CPU timing says nothing here)")
+    dev = _probe.device("foldin_probe")
     from lgcn_amd import foldin, recommend, synth
 
-    dev = torch.device("cuda")
     g = synth.ml25m_shaped(seed=0, scale=args.scale)
     U, I = g.num_users, g.num_items
     ei = torch.from_numpy(g.edge_index).to(dev)
@@ -79,29 +66,11 @@ def main():
             "topk": lambda: recommend.topk_rows(rows, picked, table, k, excl=seen, index_dtype=torch.int32),
             "served": served,
             "longest": lambda: foldin.fold_in_rows((ptr, sidx, heavy), table, isd=isd).rows}
-
-    def timed(fn):
-        torch.cuda.synchronize()
-        t = time.perf_counter()
-        out = fn()
-        torch.cuda.synchronize()
-        return out, (time.perf_counter() - t) * 1e3
-
-    results, times = {}, {name: [] for name in arms}
-    for name, fn in arms.items():  # warm-up: code objects, allocator pools
-        results[name], _ = timed(fn)
-    for _ in range(args.reps):
-        for name, fn in arms.items():
-            _, ms = timed(fn)
-            times[name].append(ms)
-            print(f"{name}: {ms:.3f} ms", flush=True)
+    results, times = _probe.run_arms(arms, args.reps, 3)
     rec = dict(histories=U, items=I, dim=args.dim, k=k, entries=int(sidx.numel()), longest_history=int(length.max()),
                mean_history=round(float(length.float().mean()), 2),
                long_histories=int((length > foldin.LONG).sum()), reps=args.reps)
-    for name, ts in times.items():
-        rec[f"{name}_ms"] = round(sorted(ts)[len(ts) // 2], 3)
-        rec[f"{name}_ms_range"] = [round(min(ts), 3), round(max(ts), 3)]
-        rec[f"{name}_ms_all"] = [round(t, 3) for t in ts]
+    _probe.put_times(rec, times, 3, spread=True)
     rec["torch_over_foldin"] = round(rec["torch_ms"] / rec["foldin_ms"], 3)
     rec["foldin_cost_ms"] = round(rec["served_ms"] - rec["topk_ms"], 3)
     rec["longest_share_of_foldin"] = round(rec["longest_ms"] / rec["foldin_ms"], 3)
@@ -113,12 +82,7 @@ def main():
     rec["torch_bitwise_repeatable"] = bool(torch.equal(theirs, torch_foldin(ptr, sidx, table, isd)))
     rec["longest_equals_batch_row"] = bool(torch.equal(results["longest"][0], ours[heavy[0]]))
     rec["served_equals_topk"] = bool(torch.equal(results["served"][0], results["topk"][0]))
-    line = json.dumps(rec)
-    print(line, flush=True)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(line + "\n")
+    _probe.emit(rec, args.out)
 
 
 if __name__ == "__main__":

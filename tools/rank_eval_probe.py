@@ -13,16 +13,9 @@ Times two things, host clock around a device synchronise, after a warm-up of eac
 The last line is one JSON record (the medians, the ratio, whether the two agree, the metrics).
 (tools/eval_probe.py is the older probe of the reference-style evaluate().)
 """
-import argparse
-import json
-import os
-import sys
-import time
-
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "movie-recommender-system-with-gnns_amd"))
+import _probe
 
 KS = (5, 10, 20)
 HELD_OUT = 5
@@ -60,18 +53,12 @@ def torch_counts(ranked, truth, rows, cs, M):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--reps", type=int, default=5)
+    ap = _probe.parser(reps=5)
     ap.add_argument("--inner", type=int, default=10)
-    ap.add_argument("--scale", type=float, default=1.0)
-    ap.add_argument("--dim", type=int, default=64)
-    ap.add_argument("--out", default=None)
     args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("rank_eval_probe needs a ROCm device (a CPU timing says nothing here)")
+    dev = _probe.device("rank_eval_probe")
     from lgcn_amd import metrics, recommend, synth
 
-    dev = torch.device("cuda")
     g = synth.ml25m_shaped(seed=0, scale=args.scale)
     U, I = g.num_users, g.num_items
     gen = torch.Generator(device=dev).manual_seed(0)
@@ -82,34 +69,14 @@ def main():
     item_emb = torch.randn(I, args.dim, device=dev, generator=gen)
     users = torch.nonzero(truth[0][1:] > truth[0][:-1]).view(-1)
 
-    def timed(fn, n=1):
-        torch.cuda.synchronize()
-        t = time.perf_counter()
-        for _ in range(n):
-            out = fn()
-        torch.cuda.synchronize()
-        return out, (time.perf_counter() - t) * 1e3 / n
-
-    whole = lambda: metrics.evaluate_ranking(user_emb, item_emb, truth, ks=KS, seen=seen)
-    result, _ = timed(whole)  # warm-up: code objects, allocator pools
-    t_whole = []
-    for _ in range(args.reps):
-        _, ms = timed(whole)
-        t_whole.append(ms)
-        print(f"evaluate_ranking: {ms:.2f} ms", flush=True)
+    whole = {"evaluate_ranking": lambda: metrics.evaluate_ranking(user_emb, item_emb, truth, ks=KS, seen=seen)}
+    result, t_whole = (d["evaluate_ranking"] for d in _probe.run_arms(whole, args.reps, 2))
 
     ranked, _ = recommend.topk_items(user_emb, item_emb, users, KS[-1], seen=seen, index_dtype=torch.int32)
     arms = {"kernel": lambda: metrics.rank_metrics(ranked, truth, KS, rows=users),
             "torch": lambda: torch_counts(ranked, truth, users, KS, I)}
-    outs, times = {}, {name: [] for name in arms}
-    for name, fn in arms.items():
-        outs[name], _ = timed(fn)
-    for _ in range(args.reps):
-        for name, fn in arms.items():
-            _, ms = timed(fn, args.inner)
-            times[name].append(ms)
-            print(f"metric stage, {name}: {ms:.3f} ms", flush=True)
-    med = lambda ts: sorted(ts)[len(ts) // 2]
+    outs, times = _probe.run_arms(arms, args.reps, 3, inner=args.inner, label="metric stage, ")
+    med = _probe.median
     a, b = outs["kernel"], outs["torch"]
     rec = dict(users=U, items=I, dim=args.dim, ks=list(KS), evaluated_users=int(users.numel()),
                seen_entries=int(seen[1].numel()), truth_entries=int(truth[1].numel()), reps=args.reps,
@@ -121,12 +88,7 @@ def main():
     rec["counts_equal"] = bool(torch.equal(a.hits, b[0]) and torch.equal(a.first, b[2]) and torch.equal(a.n_truth, b[3]))
     rec["max_dcg_diff"] = float((a.dcg - b[1]).abs().max())
     rec["metrics"] = {key: round(v, 6) for key, v in result.items()}
-    line = json.dumps(rec)
-    print(line, flush=True)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(line + "\n")
+    _probe.emit(rec, args.out)
 
 
 if __name__ == "__main__":

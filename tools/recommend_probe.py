@@ -11,16 +11,9 @@ one JSON record (ms per 1,000 users of each, their ratio, and how many of the tw
 agree). The split between the score filter and the ranked selection comes from a kernel trace of
 `--only ours` in a run of its own (rocprofv3 --kernel-trace --stats -- python tools/...).
 """
-import argparse
-import json
-import os
-import sys
-import time
-
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "movie-recommender-system-with-gnns_amd"))
+import _probe
 
 TORCH_BLOCK = 8192  # users per torch.mm block: a 1.9 GB score block at 59,047 items
 
@@ -45,19 +38,13 @@ def torch_topk(user_emb, item_emb, users, k, seen):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--reps", type=int, default=3)
-    ap.add_argument("--scale", type=float, default=1.0)
-    ap.add_argument("--dim", type=int, default=64)
+    ap = _probe.parser(reps=3)
     ap.add_argument("--k", type=int, default=10)
     ap.add_argument("--only", choices=["ours", "torch"], default=None)
-    ap.add_argument("--out", default=None)
     args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("recommend_probe needs a ROCm device (a CPU timing says nothing here)")
+    dev = _probe.device("recommend_probe")
     from lgcn_amd import recommend, synth
 
-    dev = torch.device("cuda")
     g = synth.ml25m_shaped(seed=0, scale=args.scale)
     U, I = g.num_users, g.num_items
     seen = recommend.seen_csr(torch.from_numpy(g.edge_index).to(dev), U, I, by="user")
@@ -69,37 +56,17 @@ def main():
             "torch": lambda: torch_topk(user_emb, item_emb, users, args.k, seen)}
     if args.only:
         arms = {args.only: arms[args.only]}
-
-    def timed(fn):
-        torch.cuda.synchronize()
-        t = time.perf_counter()
-        out = fn()
-        torch.cuda.synchronize()
-        return out, (time.perf_counter() - t) * 1e3
-
-    results, times = {}, {name: [] for name in arms}
-    for name, fn in arms.items():  # warm-up: code objects, allocator pools
-        results[name], _ = timed(fn)
-    for _ in range(args.reps):
-        for name, fn in arms.items():
-            _, ms = timed(fn)
-            times[name].append(ms)
-            print(f"{name}: {ms:.1f} ms", flush=True)
+    results, times = _probe.run_arms(arms, args.reps, 1)
     rec = dict(users=U, items=I, dim=args.dim, k=args.k, seen_entries=int(seen[1].numel()), reps=args.reps)
     for name, ts in times.items():
-        rec[f"{name}_ms_per_1000_users"] = round(sorted(ts)[len(ts) // 2] / U * 1000, 4)
+        rec[f"{name}_ms_per_1000_users"] = round(_probe.median(ts) / U * 1000, 4)
         rec[f"{name}_ms_all"] = [round(t, 1) for t in ts]
     if len(arms) == 2:
         rec["torch_over_ours"] = round(rec["torch_ms_per_1000_users"] / rec["ours_ms_per_1000_users"], 3)
         rec["same_index_share"] = round(float((results["ours"][0] == results["torch"][0]).float().mean()), 6)
         diff = (results["ours"][1] - results["torch"][1]).abs()
         rec["max_score_diff"] = float(diff[torch.isfinite(diff)].max())
-    line = json.dumps(rec)
-    print(line, flush=True)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(line + "\n")
+    _probe.emit(rec, args.out)
 
 
 if __name__ == "__main__":

@@ -17,16 +17,9 @@ the two arms picked the same item, and the mean ILD@k of the relevance lists and
 ones. The kernel's own time comes from a kernel trace in a run of its own
 (rocprofv3 --kernel-trace --stats -- python tools/rerank_probe.py --reps 1).
 """
-import argparse
-import json
-import os
-import sys
-import time
-
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "movie-recommender-system-with-gnns_amd"))
+import _probe
 
 TORCH_BLOCK = 8192  # users per block: a 210 MB gather and a 328 MB Gram at pool 100, d = 64
 
@@ -60,20 +53,14 @@ def torch_mmr(pool_idx, pool_score, candidates, k, diversity):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--reps", type=int, default=3)
-    ap.add_argument("--scale", type=float, default=1.0)
-    ap.add_argument("--dim", type=int, default=64)
+    ap = _probe.parser(reps=3)
     ap.add_argument("--pool", type=int, default=100)
     ap.add_argument("--k", type=int, default=10)
     ap.add_argument("--diversity", type=float, default=0.5)
-    ap.add_argument("--out", default=None)
     args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("rerank_probe needs a ROCm device (a CPU timing says nothing here)")
+    dev = _probe.device("rerank_probe")
     from lgcn_amd import recommend, synth
 
-    dev = torch.device("cuda")
     g = synth.ml25m_shaped(seed=0, scale=args.scale)
     U, I = g.num_users, g.num_items
     seen = recommend.seen_csr(torch.from_numpy(g.edge_index).to(dev), U, I, by="user")
@@ -90,27 +77,10 @@ def main():
                                                            index_dtype=torch.int32),
             "rerank": lambda: recommend.rerank_mmr(pool_idx, pool_score, item_emb, k, delta),
             "torch": lambda: torch_mmr(pool_idx64, pool_score, item_emb, k, delta)}
-
-    def timed(fn):
-        torch.cuda.synchronize()
-        t = time.perf_counter()
-        out = fn()
-        torch.cuda.synchronize()
-        return out, (time.perf_counter() - t) * 1e3
-
-    results, times = {}, {name: [] for name in arms}
-    for name, fn in arms.items():  # warm-up: code objects, allocator pools
-        results[name], _ = timed(fn)
-    for _ in range(args.reps):
-        for name, fn in arms.items():
-            _, ms = timed(fn)
-            times[name].append(ms)
-            print(f"{name}: {ms:.1f} ms", flush=True)
+    results, times = _probe.run_arms(arms, args.reps, 1)
     rec = dict(users=U, items=I, dim=args.dim, pool=N, k=k, diversity=delta, seen_entries=int(seen[1].numel()),
                reps=args.reps)
-    for name, ts in times.items():
-        rec[f"{name}_ms"] = round(sorted(ts)[len(ts) // 2], 2)
-        rec[f"{name}_ms_all"] = [round(t, 2) for t in ts]
+    _probe.put_times(rec, times, 2)
     rec["torch_over_rerank"] = round(rec["torch_ms"] / rec["rerank_ms"], 3)
     ours, (t_idx, t_pair) = results["rerank"], results["torch"]
     rec["same_pick_share"] = round(float((ours.idx.to(torch.int64) == t_idx).float().mean()), 6)
@@ -121,12 +91,7 @@ def main():
     rec[f"ild@{k}_reranked"] = round(float(recommend.intra_list_diversity(ours.pair, ours.n, ks).mean()), 6)
     n_t = torch.full((t_pair.shape[0],), k, device=dev)
     rec[f"ild@{k}_torch"] = round(float(recommend.intra_list_diversity(t_pair, n_t, ks).mean()), 6)
-    line = json.dumps(rec)
-    print(line, flush=True)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(line + "\n")
+    _probe.emit(rec, args.out)
 
 
 if __name__ == "__main__":
