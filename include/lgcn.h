@@ -778,6 +778,48 @@ int lgcn_foldin_rows(const int64_t* hist_ptr, const int32_t* hist_idx, const flo
                      const float* table, int64_t M, int32_t d, int64_t ldt, const float* isd,
                      float* out, int64_t ldo, int32_t* out_n, lgcn_stream_t stream);
 
+/* BPR negatives (added under ABI 11, purely additive): per triplet b < B one item its user has no
+ * train edge to, drawn exactly uniformly over the unseen items without rejection (n == 1), or the
+ * one of n such draws the model scores highest (dynamic negative sampling, n > 1)
+ * (csrc/lgcn_negatives.hip: a thread per triplet; for n > 1 a 16-lane group per triplet).
+ *   users int64[B]; first: the global index of triplet 0, so that triplet b draws as triplet
+ *     first + b of a longer list does.
+ *   seen: CSR (seen_ptr int64[seen_rows + 1], seen_idx int32), row u the items user u has seen,
+ *     ascending, distinct and within [0, I) (lgcn_amd.recommend.seen_csr); a user outside
+ *     [0, seen_rows) has an empty row. Both pointers NULL: nothing is excluded.
+ *   The draw, all arithmetic mod 2^64, G = 0x9E3779B97F4A7C15:
+ *       mix(z): z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27; z *= 0x94D049BB133111EB; z ^= z >> 31
+ *       h0 = mix(seed + G * (step + 1));  h1 = mix(h0 ^ (first + b));  h2 = mix(h1 + G * (j + 1))
+ *     With s[0 .. c) the user's row and m = I - c: candidate j is the r-th item (from 0) outside the
+ *     row, r = umul64hi(h2, m) — r + t with t the number of positions p with s[p] - p <= r. When
+ *     m <= 0 (the user has seen everything) candidate j is umul64hi(h2, I) and stats[0] counts the
+ *     triplet. Every candidate is in [0, I).
+ *   n == 1: out[b] = candidate 0; out_score[b] = 0. The tables are not read and may be NULL.
+ *   n > 1: user_rows [U, d] and item_rows [at least I, d] f32 at strides ldu, ldi >= d floats, d a
+ *     multiple of 4, bases and strides multiples of 16 bytes. Candidate j scores
+ *     dot / (sqrtf(|u|^2) * sqrtf(|c_j|^2)), the three sums in f32 (summation order unspecified, a
+ *     function of d alone) over user_rows[users[b]] and item_rows[candidate j]. out[b] is the
+ *     candidate with the largest score, the lowest j among equal scores; a NaN score (a zero row
+ *     gives 0 / 0) ranks as -inf, -0 as +0. out_score[b] is that score as computed. A user outside
+ *     [0, U) reads no row: out[b] = candidate 0, out_score[b] = NaN, stats[1] counts the triplet.
+ *   out int64[B]; out_score f32[B] (nullable); stats int64[2] is added to, never reset.
+ *   The same (seed, step, first + b, users[b]) gives the same bits for any B, any split into calls,
+ *   and run to run. The only atomics are the adds to stats, one per workgroup and counter.
+ * LGCN_E_ARG: a null users, out or stats, one of seen_ptr / seen_idx null without the other, B, first
+ * or seen_rows below 0, B above INT32_MAX, I outside [1, INT32_MAX], n < 1; for n > 1 a null table,
+ * U < 0, d < 4 or no multiple of 4, a stride below d, no multiple of 4 or above INT32_MAX, a
+ * misaligned base. LGCN_E_UNSUPPORTED: n > LGCN_NEGATIVES_MAX_N, d > LGCN_NEGATIVES_MAX_D. Checked
+ * before any HIP call; B == 0 returns LGCN_OK without a launch. Allocates nothing, reads nothing
+ * back, does not synchronise, needs no workspace. */
+#define LGCN_NEGATIVES_MAX_N 32    /* candidates per triplet */
+#define LGCN_NEGATIVES_MAX_D 512   /* columns of a table row */
+int lgcn_sample_negatives(const int64_t* users, int64_t B, int64_t first,
+                          const int64_t* seen_ptr, const int32_t* seen_idx, int64_t seen_rows,
+                          int64_t I, uint64_t seed, int64_t step, int32_t n,
+                          const float* user_rows, int64_t ldu, int64_t U,
+                          const float* item_rows, int64_t ldi, int32_t d,
+                          int64_t* out, float* out_score, int64_t* stats, lgcn_stream_t stream);
+
 /* Host-only (no GPU): `draws` consecutive numpy legacy np.random.choice(n, size, replace=False)
  * calls (reference utils/train_test.py:187) on the MT19937 state (key[624], *pos) of
  * np.random.get_state(), written to out[draws*size]; key/pos are advanced exactly as numpy would

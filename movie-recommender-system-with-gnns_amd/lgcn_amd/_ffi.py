@@ -37,6 +37,8 @@ EXPLAIN_MAX_R = 8  # LGCN_EXPLAIN_MAX_R
 FOLDIN_MAX_D = 256  # LGCN_FOLDIN_MAX_D
 FOLDIN_LONG = 512  # LGCN_FOLDIN_LONG: history entries above which eight waves share a history
 FOLDIN_CHUNK = 512  # LGCN_FOLDIN_CHUNK: entries of one wave's chunk of a long history
+NEGATIVES_MAX_N = 32  # LGCN_NEGATIVES_MAX_N
+NEGATIVES_MAX_D = 512  # LGCN_NEGATIVES_MAX_D
 
 _lib = None
 
@@ -146,6 +148,8 @@ _SIGS = {
     "lgcn_explain_topr": ([_vp, _i64, _i32, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp,
                            _vp], ctypes.c_int),
     "lgcn_foldin_rows": ([_vp, _vp, _vp, _vp, _i64, _i64, _vp, _i64, _i32, _i64, _vp, _vp, _i64, _vp, _vp], ctypes.c_int),
+    "lgcn_sample_negatives": ([_vp, _i64, _i64, _vp, _vp, _i64, _i64, ctypes.c_uint64, _i64, _i32, _vp, _i64, _i64, _vp,
+                               _i64, _i32, _vp, _vp, _vp, _vp], ctypes.c_int),
     "lgcn_legacy_choice": ([_vp, _vp, _i64, _i64, _i64, _vp], ctypes.c_int),
     "lgcn_slice_schedule_workspace_size": ([_i64, _i64, _i32, _i32, _vp, _vp], ctypes.c_int),
     "lgcn_slice_schedule_build": ([_vp, _vp, _i64, _i64, _vp, _i32, _i32, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp,
@@ -237,7 +241,7 @@ CSRC = _HERE.parent / "csrc"
 INCLUDE = _HERE.parent.parent / "include"
 # the translation units of liblgcn.so (lgcn_build.cpp carries the hash and is not hashed)
 SOURCES = ("lgcn_plan.hip", "lgcn_spmm.hip", "lgcn_optim.hip", "lgcn_bpr.hip", "lgcn_recall.hip", "lgcn_metrics.hip", "lgcn_rerank.hip",
-           "lgcn_explain.hip", "lgcn_foldin.hip", "lgcn_rowadam.hip", "lgcn_exchange.hip", "lgcn_partition.cpp", "lgcn_sample.cpp", "lgcn_tuning.cpp", "lgcn_program.cpp")
+           "lgcn_explain.hip", "lgcn_foldin.hip", "lgcn_negatives.hip", "lgcn_rowadam.hip", "lgcn_exchange.hip", "lgcn_partition.cpp", "lgcn_sample.cpp", "lgcn_tuning.cpp", "lgcn_program.cpp")
 # the headers they include (csrc/), hashed and tracked as build dependencies with include/lgcn.h
 HEADERS = ("lgcn_common.h", "lgcn_exact.h", "lgcn_reg.h", "lgcn_ragged.h")
 

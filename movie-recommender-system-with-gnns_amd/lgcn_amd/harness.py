@@ -200,6 +200,18 @@ class _Sampler:
         else:
             out.copy_(self(pos))
 
+    def draw_triplets(self, out, users, pos, step=None) -> None:
+        """The step's draw: by the sampler utils.helpers.set_negative_sampler installed (on its own
+        step counter — the step's restarts with every new (model, optimizer) pair, the sampler's
+        never repeats a draw), else draw_into's."""
+        sampler = self.helpers.negative_sampler()
+        if sampler is None:
+            self.draw_into(out, pos)
+        elif hasattr(sampler, "draw_triplets"):
+            sampler.draw_triplets(out, users, pos)
+        else:
+            out.copy_(sampler(users, pos))
+
 
 _FAST: "weakref.WeakKeyDictionary[torch.optim.Optimizer, _Fast]" = weakref.WeakKeyDictionary()
 

@@ -434,6 +434,8 @@ class FusedTrainStep:
         neg_sampler (pos_items [B] -> item ids [B]): draw the negatives with it (the harness passes
         utils.helpers.sample_negative, so what that function draws — patched or not — is what the
         step trains on); default: torch.randint(0, I, (B,)) into the batch's buffer, the same draws.
+        A sampler with draw_triplets(out, users, pos, step) — lgcn_amd.negatives.NegativeSampler:
+        unseen items only, hardest of n — writes step k's negatives into the batch's buffer itself.
         loss_acc (lazy; device float64 [1]): each step adds double(loss) * its batch's edge count to
         it (lgcn_loss_accumulate, inside the captured step) — the harness's epoch-loss sum."""
         self.model = model
@@ -514,7 +516,9 @@ class FusedTrainStep:
         dev = m.user_embedding.weight.device
         k = self._k if k is None else k
         if self.neg_sampler is not None:
-            if hasattr(self.neg_sampler, "draw_into"):
+            if hasattr(self.neg_sampler, "draw_triplets"):  # a sampler that reads the users (lgcn_amd.negatives)
+                self.neg_sampler.draw_triplets(st.neg, st.users, st.pos, k)
+            elif hasattr(self.neg_sampler, "draw_into"):
                 self.neg_sampler.draw_into(st.neg, st.pos)
             else:
                 st.neg.copy_(self.neg_sampler(st.pos))
