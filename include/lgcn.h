@@ -820,6 +820,58 @@ int lgcn_sample_negatives(const int64_t* users, int64_t B, int64_t first,
                           const float* item_rows, int64_t ldi, int32_t d,
                           int64_t* out, float* out_score, int64_t* stats, lgcn_stream_t stream);
 
+/* Exact full-ranking positions (added under ABI 11, purely additive): for every (query, held-out
+ * item) pair, how many eligible candidates stand above the item under lgcn_select_topk_ranked's
+ * rule — what AUC, mean percentile rank and an uncapped MRR are made of, and the answer to "where
+ * does item j rank for this query". No [Q, M] score matrix and no candidate lists exist at any
+ * point (csrc/lgcn_rankpos.hip).
+ *   Qn [Qpad, D], Cn [M, D]: unit rows as lgcn_normalize_rows writes them, both 16-byte aligned, D
+ *     one of lgcn_recall_width's widths, Qpad a multiple of 128. Rows [Q, Qpad) of Qn are read and
+ *     what they hold is ignored (zeros, or the next queries of a longer table).
+ *   truth: CSR (truth_ptr int64[truth_rows + 1], truth_idx int32) and seen: CSR (seen_ptr
+ *     int64[seen_rows + 1], seen_idx int32 ascending and distinct within a row; seen_ptr NULL:
+ *     nothing is seen), both with the row conventions of the exclusion CSR above: query q uses row
+ *     truth_row[q] / seen_row[q] (row q when that pointer is NULL); a row outside the CSR is empty.
+ *     Rows may be arbitrarily long.
+ *   out_ptr int64[Q + 1]: the prefix sums of the queries' truth-row lengths, out_ptr[Q] = nnz; entry
+ *     t of query q's truth row is slot out_ptr[q] + t of the outputs.
+ *   key(q, i): exactly the uint32 key lgcn_score_filter gives the pair, bit for bit (the same
+ *     v_mfma_f32_32x32x2_f32 chain, step s covering columns s and D/2 + s; NaN is 0xFFFFFFFF).
+ *   i beats j when key(q, i) > key(q, j), or the keys are equal and i < j.
+ *   pos_out[slot]  = #{ i in [0, M) outside the seen row : i beats j } for the slot's item j, when
+ *                    0 <= j < M and j is not in the seen row (other truth entries count as
+ *                    candidates); -1 otherwise: such an item can never be ranked.   (int32 [nnz])
+ *     So pos = p < k exactly when lgcn_select_topk_ranked puts j at slot p of the query's list.
+ *   key_out[slot]  = key(q, j); 0 for j outside [0, M).                            (uint32 [nnz])
+ *   eligible_out[q] = M - |seen row within [0, M)|.                                (int32 [Q])
+ *   workspace: lgcn_rank_positions_workspace_size(Q, nnz) bytes, 256-byte aligned.
+ *   stages: LGCN_RANKPOS_ALL. The call issues three stages — the targets' keys (which also zeroes
+ *     the counts), the dense count over all candidates, the seen correction that finishes pos_out and
+ *     writes eligible_out — and a mask of LGCN_RANKPOS_KEYS / _COUNT / _FINISH issues only those, on
+ *     the buffers the earlier stages of a previous call left (for timing a stage on its own; the
+ *     outputs are the documented ones only after all three ran once each, in order).
+ * The counts are integer sums (one int32 atomic per (query, target) and candidate chunk), so the
+ * outputs are bitwise reproducible, and the same (query, item, seen row) gives the same position
+ * alone or in a batch, at any batch position.
+ * LGCN_E_ARG: a null required pointer (truth_row, seen_ptr, seen_idx, seen_row may be NULL; seen_idx
+ * must be set when seen_ptr is), Q < 0, Qpad < Q, Qpad not a multiple of 128, M, nnz, truth_rows or
+ * seen_rows below 0, M or Qpad above INT32_MAX, a misaligned Qn, Cn or workspace, stages outside
+ * [1, LGCN_RANKPOS_ALL].
+ * LGCN_E_UNSUPPORTED: D not one of lgcn_recall_width's widths. LGCN_E_WORKSPACE: workspace too small
+ * or null. Checked before any HIP call; Q == 0 or nnz == 0 returns LGCN_OK without a launch (and
+ * writes nothing). Allocates nothing, reads nothing back, does not synchronise. */
+#define LGCN_RANKPOS_KEYS 1
+#define LGCN_RANKPOS_COUNT 2
+#define LGCN_RANKPOS_FINISH 4
+#define LGCN_RANKPOS_ALL 7
+int lgcn_rank_positions_workspace_size(int64_t Q, int64_t nnz, size_t* bytes);
+int lgcn_rank_positions(const float* Qn, int64_t Qpad, int64_t Q, const float* Cn, int64_t M, int32_t D,
+                        const int64_t* truth_ptr, const int32_t* truth_idx, const int64_t* truth_row,
+                        int64_t truth_rows, const int64_t* seen_ptr, const int32_t* seen_idx,
+                        const int64_t* seen_row, int64_t seen_rows, const int64_t* out_ptr, int64_t nnz,
+                        int32_t* pos_out, uint32_t* key_out, int32_t* eligible_out, void* workspace,
+                        size_t workspace_bytes, int32_t stages, lgcn_stream_t stream);
+
 /* Host-only (no GPU): `draws` consecutive numpy legacy np.random.choice(n, size, replace=False)
  * calls (reference utils/train_test.py:187) on the MT19937 state (key[624], *pos) of
  * np.random.get_state(), written to out[draws*size]; key/pos are advanced exactly as numpy would

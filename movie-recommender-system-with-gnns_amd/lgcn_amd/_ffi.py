@@ -39,6 +39,7 @@ FOLDIN_LONG = 512  # LGCN_FOLDIN_LONG: history entries above which eight waves s
 FOLDIN_CHUNK = 512  # LGCN_FOLDIN_CHUNK: entries of one wave's chunk of a long history
 NEGATIVES_MAX_N = 32  # LGCN_NEGATIVES_MAX_N
 NEGATIVES_MAX_D = 512  # LGCN_NEGATIVES_MAX_D
+RANKPOS_KEYS, RANKPOS_COUNT, RANKPOS_FINISH, RANKPOS_ALL = 1, 2, 4, 7  # LGCN_RANKPOS_*: lgcn_rank_positions' stages
 
 _lib = None
 
@@ -150,6 +151,9 @@ _SIGS = {
     "lgcn_foldin_rows": ([_vp, _vp, _vp, _vp, _i64, _i64, _vp, _i64, _i32, _i64, _vp, _vp, _i64, _vp, _vp], ctypes.c_int),
     "lgcn_sample_negatives": ([_vp, _i64, _i64, _vp, _vp, _i64, _i64, ctypes.c_uint64, _i64, _i32, _vp, _i64, _i64, _vp,
                                _i64, _i32, _vp, _vp, _vp, _vp], ctypes.c_int),
+    "lgcn_rank_positions_workspace_size": ([_i64, _i64, ctypes.POINTER(_sz)], ctypes.c_int),
+    "lgcn_rank_positions": ([_vp, _i64, _i64, _vp, _i64, _i32, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _i64,
+                             _vp, _vp, _vp, _vp, _sz, _i32, _vp], ctypes.c_int),
     "lgcn_legacy_choice": ([_vp, _vp, _i64, _i64, _i64, _vp], ctypes.c_int),
     "lgcn_slice_schedule_workspace_size": ([_i64, _i64, _i32, _i32, _vp, _vp], ctypes.c_int),
     "lgcn_slice_schedule_build": ([_vp, _vp, _i64, _i64, _vp, _i32, _i32, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp,
@@ -241,7 +245,7 @@ CSRC = _HERE.parent / "csrc"
 INCLUDE = _HERE.parent.parent / "include"
 # the translation units of liblgcn.so (lgcn_build.cpp carries the hash and is not hashed)
 SOURCES = ("lgcn_plan.hip", "lgcn_spmm.hip", "lgcn_optim.hip", "lgcn_bpr.hip", "lgcn_recall.hip", "lgcn_metrics.hip", "lgcn_rerank.hip",
-           "lgcn_explain.hip", "lgcn_foldin.hip", "lgcn_negatives.hip", "lgcn_rowadam.hip", "lgcn_exchange.hip", "lgcn_partition.cpp", "lgcn_sample.cpp", "lgcn_tuning.cpp", "lgcn_program.cpp")
+           "lgcn_explain.hip", "lgcn_foldin.hip", "lgcn_negatives.hip", "lgcn_rankpos.hip", "lgcn_rowadam.hip", "lgcn_exchange.hip", "lgcn_partition.cpp", "lgcn_sample.cpp", "lgcn_tuning.cpp", "lgcn_program.cpp")
 # the headers they include (csrc/), hashed and tracked as build dependencies with include/lgcn.h
 HEADERS = ("lgcn_common.h", "lgcn_exact.h", "lgcn_reg.h", "lgcn_ragged.h")
 

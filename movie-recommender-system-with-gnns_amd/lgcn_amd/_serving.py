@@ -1,7 +1,7 @@
 """Argument handling shared by the serving modules (recommend, explain, foldin, metrics): one check
 of a ragged-CSR argument, one int32 image of an index list, the kernels' padded row width, the
 candidates' unit rows, and the per-entry weights check. ``who`` is the caller's message prefix
-("recommend", "explain", "fold_in", "rank_metrics"). Nothing here loads the library; moving tensors
+("recommend", "explain", "fold_in", "rank_metrics", "rank_positions"). Nothing here loads the library; moving tensors
 to a device stays with the callers.
 """
 from __future__ import annotations

@@ -18,6 +18,12 @@ each averaged over the users with T > 0 (``users`` in the result).
 With evaluate_ranking(diversity=...) the lists are recommend.topk_rows_diverse's (greedy MMR over a
 relevance pool) and the result also carries ild@c, the mean intra-list diversity
 (recommend.intra_list_diversity) over the evaluated users with at least two listed items.
+
+Below the cutoff (no cap of 1,024, no lists): rank_positions gives every (user, held-out item) pair
+its exact 0-based position in the user's full ranking (lgcn_rank_positions, csrc/lgcn_rankpos.hip:
+a counting pass over all items on the ranking kernels' f32 MFMA keys, the same order and tie rule
+as the lists above), summarize_positions turns positions into AUC, mean percentile rank, MRR, mean
+rank and the metrics above at ANY cutoffs, and evaluate_auc is the two for an embedding pair.
 """
 from __future__ import annotations
 
@@ -186,3 +192,252 @@ def evaluate_ranking(user_emb: torch.Tensor, item_emb: torch.Tensor, truth, ks=(
         return out
     ranked, _ = recommend.topk_items(user_emb, item_emb, users, cs[-1], seen=seen, index_dtype=torch.int32, **topk_kw)
     return summarize(rank_metrics(ranked, (ptr, idx), cs, rows=users), cs)
+
+
+class RankPositions(NamedTuple):
+    """lgcn_rank_positions' outputs for Q queries whose truth rows hold nnz entries, on the device."""
+    ptr: torch.Tensor       # int64 [Q + 1]: query q's entries are ptr[q] .. ptr[q + 1], in truth-row order
+    pos: torch.Tensor       # int32 [nnz]: eligible candidates ranked above the item; -1: seen or outside [0, M)
+    score: torch.Tensor     # f32 [nnz]: the score behind the item's key (NaN for an item outside [0, M))
+    eligible: torch.Tensor  # int32 [Q]: candidates the query's seen row leaves
+
+
+def _row_lengths(ptr: torch.Tensor, rows: torch.Tensor | None, Q: int) -> torch.Tensor:
+    """int64 [Q]: the length of each query's row of the CSR ptr (rows[q], or q); 0 outside the CSR."""
+    R = ptr.numel() - 1
+    r = torch.arange(Q, device=ptr.device) if rows is None else rows
+    if R == 0:
+        return torch.zeros(Q, dtype=torch.int64, device=ptr.device)
+    inside = (r >= 0) & (r < R)
+    rc = r.clamp(0, R - 1)
+    return torch.where(inside, ptr[rc + 1] - ptr[rc], torch.zeros_like(rc)).clamp(min=0)
+
+
+# truth-row lengths above which queries (sorted longest row first) are issued as a call of their own
+TIER_LENGTHS = (256, 32)
+
+
+def _tiers(Q: int, longer) -> list:
+    """[a, b) query ranges of rank_positions' calls: queries sorted longest truth row first, longer[i]
+    of them with rows above TIER_LENGTHS[i]; boundaries on the kernels' 128-query groups. The dense
+    count splits the candidates over about 2048 workgroups per call and a query group runs its
+    passes one after the other, so the few queries with very long rows get a call of their own, in
+    which each workgroup's share of the candidates (one pass) is short."""
+    cuts = sorted({min(Q, -(-int(n) // 128) * 128) for n in longer} | {0, Q})
+    return [(a, b) for a, b in zip(cuts[:-1], cuts[1:])]
+
+
+def _issue_positions(lib, tiers, Qn, D, Cn, M, tptr, tidx, trow, sptr, sidx, srow, out_ptr, nnz, pos, key, eligible,
+                     ws, stages, stream) -> None:
+    """lgcn_rank_positions for each tier's queries: a slice of the query-indexed arrays, the whole of
+    the entry-indexed ones (out_ptr holds absolute slots)."""
+    for a, b in tiers:
+        at = lambda t, width=8: None if t is None else t.data_ptr() + a * width
+        _ffi.check(lib.lgcn_rank_positions(at(Qn, D * 4), -(-(b - a) // 128) * 128, b - a, Cn.data_ptr(), M, D,
+                                           tptr.data_ptr() + (a * 8 if trow is None else 0),
+                                           tidx.data_ptr() if tidx.numel() else ws.data_ptr(), at(trow),
+                                           tptr.numel() - 1 - (a if trow is None else 0),
+                                           None if sptr is None else sptr.data_ptr() + (a * 8 if srow is None else 0),
+                                           _ffi.ptr(sidx), at(srow),
+                                           0 if sptr is None else sptr.numel() - 1 - (a if srow is None else 0),
+                                           at(out_ptr), nnz, pos.data_ptr(), key.data_ptr(), at(eligible, 4),
+                                           ws.data_ptr(), ws.numel(), stages, stream), "lgcn_rank_positions")
+
+
+def rank_positions(queries: torch.Tensor, picked, candidates: torch.Tensor, truth, seen=None, rows=None,
+                   normalized: bool = False) -> RankPositions:
+    """Where each held-out item stands in its query's full ranking, on the device.
+
+    Query q is the row queries[picked[q]]; candidates [M, d] are ranked for it by cosine score as
+    recommend.topk_rows ranks them (score descending, candidate index ascending, NaN first, the
+    query's seen row left out), and for every entry j of its truth row pos is the number of eligible
+    candidates ranked above j: pos = p < k exactly when topk_rows(..., k, excl=seen) has j at slot p.
+    pos is -1 for an entry that is in the seen row or outside [0, M); other truth entries count as
+    candidates. No [Q, M] matrix and no lists exist at any point, and k is not capped.
+    truth: (ptr, idx) as recommend.seen_csr builds it; rows[q] names the truth row of query q (row q
+    when rows is None); a row outside the CSR is empty. seen: None, (ptr, idx) — row q is query q's —
+    or (ptr, idx, rows); rows ascending and distinct. Both are checked by _serving.csr_arg.
+    normalized=True takes queries and candidates as unit rows already (only zero-padded).
+    One host read: the number of truth entries (the size of pos)."""
+    who = "rank_positions"
+    if queries.dim() != 2 or candidates.dim() != 2:
+        raise ValueError(f"{who}: queries and candidates must be 2-D")
+    if queries.dtype != torch.float32 or candidates.dtype != torch.float32:
+        raise TypeError(f"{who}: queries and candidates must be float32")
+    if candidates.shape[1] != queries.shape[1]:
+        raise ValueError(f"{who}: queries and candidates must have the same width")
+    d, M = queries.shape[1], candidates.shape[0]
+    D = _serving.width(who, d)
+    picked = torch.as_tensor(picked).reshape(-1)
+    if picked.dtype.is_floating_point or picked.dtype.is_complex or picked.dtype == torch.bool:
+        raise TypeError(f"{who}: picked must be integers, got {picked.dtype}")
+    Q = picked.numel()
+    if truth is None or len(truth) != 2:
+        raise ValueError(f"{who}: truth is (ptr, idx)")
+    tptr, tidx, trow, _ = _serving.csr_arg(who, "truth", tuple(truth) if rows is None else (*truth, rows), Q, short=True)
+    sptr = sidx = srow = None
+    if seen is not None:
+        sptr, sidx, srow, _ = _serving.csr_arg(who, "seen", seen, Q)
+    lib = _ffi.load()
+    for t in (queries, candidates, tptr, tidx) + (() if seen is None else (sptr, sidx)):
+        _ffi.require_device(t, who)
+    dev = queries.device
+    s = _ffi.stream_of(dev)
+    picked = picked.to(device=dev, dtype=torch.int64).contiguous()
+    on = lambda t: None if t is None else t.to(device=dev, dtype=torch.int64).contiguous()
+    tptr, tidx, trow = tptr.to(dev).contiguous(), tidx.to(dev).contiguous(), on(trow)
+    if seen is not None:
+        sptr, sidx, srow = sptr.to(dev).contiguous(), sidx.to(dev).contiguous(), on(srow)
+        if sidx.numel() == 0:  # nothing is seen anywhere (and no device address to pass)
+            sptr = sidx = srow = None
+    out_ptr = torch.zeros(Q + 1, dtype=torch.int64, device=dev)
+    lens = _row_lengths(tptr, trow, Q)
+    if Q:
+        out_ptr[1:] = torch.cumsum(lens, 0)
+    nnz, *longer = torch.stack([out_ptr[-1]] + [(lens > n).sum() for n in TIER_LENGTHS]).tolist()  # the host read
+    # The dense count takes a workgroup's 128 queries through as many passes as their longest truth
+    # row asks for, so the queries go to the library longest row first (rows of a kind share a
+    # workgroup) and the outputs come back in the caller's order. Positions are exact counts: the
+    # order changes no value.
+    order = None
+    if Q > 128 and nnz:
+        order = torch.sort(lens, descending=True, stable=True).indices
+        ident = torch.arange(Q, device=dev)
+        picked, trow = picked[order], (ident if trow is None else trow)[order].contiguous()
+        if sptr is not None:
+            srow = (ident if srow is None else srow)[order].contiguous()
+        given_ptr, out_ptr = out_ptr, torch.zeros_like(out_ptr)
+        out_ptr[1:] = torch.cumsum(lens[order], 0)
+    pos = torch.empty(nnz, dtype=torch.int32, device=dev)
+    key = torch.empty(nnz, dtype=torch.int32, device=dev)
+    eligible = torch.empty(Q, dtype=torch.int32, device=dev)
+    if Q and nnz == 0:  # the library launches nothing without truth entries
+        if sptr is None:
+            eligible.fill_(M)
+        else:
+            inside = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev),
+                                torch.cumsum(((sidx >= 0) & (sidx < M)).to(torch.int64), 0)])
+            R = sptr.numel() - 1
+            r = torch.arange(Q, device=dev) if srow is None else srow
+            ok = (r >= 0) & (r < R)
+            rc = r.clamp(0, max(R - 1, 0))
+            n = torch.where(ok, inside[sptr[(rc + 1).clamp(max=R)]] - inside[sptr[rc]], torch.zeros_like(rc))
+            eligible.copy_(M - n)
+    elif Q:
+        Dv, qm = ctypes.c_int32(0), ctypes.c_int32(0)
+        _ffi.check(lib.lgcn_recall_width(d, ctypes.byref(Dv), ctypes.byref(qm)), "lgcn_recall_width")
+        D, qmul = Dv.value, qm.value
+        Qpad = (Q + qmul - 1) // qmul * qmul
+        queries = queries.detach()
+        if normalized:
+            Qn = torch.zeros((Qpad, D), dtype=torch.float32, device=dev)
+            Qn[:Q, :d] = queries[picked]
+        else:
+            Qn = torch.empty((Qpad, D), dtype=torch.float32, device=dev)
+            recommend._normalize_into(lib, queries, picked.data_ptr(), Q, Qn.data_ptr(), D, Qpad, s)
+        Cn = _serving.unit_rows(lib, candidates, D, normalized, s)
+        need = ctypes.c_size_t(0)
+        _ffi.check(lib.lgcn_rank_positions_workspace_size(Q, nnz, ctypes.byref(need)), "lgcn_rank_positions_workspace_size")
+        ws = torch.empty(need.value, dtype=torch.uint8, device=dev)
+        tiers = _tiers(Q, longer) if order is not None else [(0, Q)]
+        _issue_positions(lib, tiers, Qn, D, Cn, M, tptr, tidx, trow, sptr, sidx, srow, out_ptr, nnz, pos, key,
+                         eligible, ws, _ffi.RANKPOS_ALL, s)
+    if order is not None:  # back to the caller's order: query q's entries start at out_ptr[where q went]
+        went = torch.empty_like(order)
+        went[order] = torch.arange(Q, device=dev)
+        src = torch.repeat_interleave(out_ptr[went] - given_ptr[:-1], lens, output_size=nnz) + torch.arange(nnz, device=dev)
+        pos, key, eligible, out_ptr = pos[src], key[src], eligible[went], given_ptr
+    # the score behind a key (csrc/lgcn_ragged.h ordered_value; key 0, "no key", comes out a NaN)
+    bits = torch.where(key < 0, key ^ torch.iinfo(torch.int32).min, ~key)
+    return RankPositions(out_ptr, pos, bits.view(torch.float32), eligible)
+
+
+def summarize_positions(positions, ks=()) -> dict:
+    """AUC and its relatives from exact positions: {'users', 'auc', 'mpr', 'mrr', 'mean_rank'} plus
+    recall@c, precision@c, hit_rate@c, ndcg@c and mrr@c for every c of ``ks`` — any positive
+    integers, any number of them (neither MAX_CUTOFFS nor the ranked lists' 1,024 applies).
+    For a user with ranked held-out items H' = {pos >= 0}, n = |H'| and N_neg = eligible - n:
+        auc       = 1 - (sum of pos - n (n - 1) / 2) / (n * N_neg)   the share of (held-out,
+                    negative) pairs the model orders correctly: an item at position p has p - (its
+                    rank among H') negatives above it
+        mpr       = mean of pos / max(eligible - 1, 1)               0 is best
+        mrr       = 1 / (min pos + 1)
+        mean_rank = mean of pos
+    and the @c metrics exactly as the module docstring defines them, the hit ranks being the
+    positions below c and T the whole truth row (a held-out item that can never be ranked still
+    counts in T). Every value is the mean over the users with n > 0 and N_neg > 0, 'users' their
+    number; nan when there is none. Float64 torch on the tensors' device (CPU tensors work too), one
+    host read."""
+    ptr, pos, _, eligible = positions
+    cs = sorted({int(c) for c in ks})
+    if cs and cs[0] < 1:
+        raise ValueError(f"summarize_positions: cutoffs {cs} must be positive")
+    Q, nnz = eligible.numel(), pos.numel()
+    if ptr.numel() != Q + 1:
+        raise ValueError(f"summarize_positions: ptr has {ptr.numel()} entries for {Q} queries")
+    dev, f64, i64 = pos.device, torch.float64, torch.int64
+    T = (ptr[1:] - ptr[:-1]).to(i64)
+    qid = torch.repeat_interleave(torch.arange(Q, device=dev), T, output_size=nnz)
+    p = pos.to(i64)
+    ranked = p >= 0
+    per_user = lambda v: torch.zeros(Q, dtype=v.dtype, device=dev).index_add_(0, qid, v)
+    n = per_user(ranked.to(i64))
+    total = per_user(torch.where(ranked, p, torch.zeros_like(p)))
+    far = torch.iinfo(i64).max
+    first = torch.full((Q,), far, dtype=i64, device=dev).scatter_reduce_(
+        0, qid, torch.where(ranked, p, torch.full_like(p, far)), "amin")
+    elig = eligible.to(i64)
+    n_neg = elig - n
+    valid = (n > 0) & (n_neg > 0)
+    nf, tf = n.clamp(min=1).to(f64), total.to(f64)
+    cols = [1.0 - (tf - (n * (n - 1)).to(f64) / 2.0) / (nf * n_neg.clamp(min=1).to(f64)),
+            tf / nf / (elig - 1).clamp(min=1).to(f64),
+            1.0 / (first.clamp(max=far - 1) + 1).to(f64),
+            tf / nf]
+    names = ["auc", "mpr", "mrr", "mean_rank"]
+    if cs:
+        c = torch.tensor(cs, dtype=i64, device=dev)
+        hit = ranked[:, None] & (p[:, None] < c[None, :])  # [nnz, C]
+        hits = torch.zeros((Q, len(cs)), dtype=f64, device=dev).index_add_(0, qid, hit.to(f64))
+        gain = 1.0 / torch.log2((p.clamp(min=0) + 2).to(f64))
+        dcg = torch.zeros((Q, len(cs)), dtype=f64, device=dev).index_add_(
+            0, qid, torch.where(hit, gain[:, None], torch.zeros((), dtype=f64, device=dev)))
+        deep = min(cs[-1], max(nnz, 1))  # no truth row is longer than nnz
+        table = torch.cat([torch.zeros(1, dtype=f64, device=dev),
+                           torch.cumsum(1.0 / torch.log2(torch.arange(2, deep + 2, dtype=f64, device=dev)), 0)])
+        idcg = table[torch.minimum(T.clamp(min=1)[:, None], c[None, :]).clamp(max=deep)]
+        rr = torch.where(first[:, None] < c[None, :], 1.0 / (first.clamp(max=far - 1) + 1).to(f64)[:, None],
+                         torch.zeros((), dtype=f64, device=dev))
+        per_c = [hits / T.clamp(min=1).to(f64)[:, None], hits / c.to(f64)[None, :], (hits > 0).to(f64), dcg / idcg, rr]
+    w = valid.to(f64)
+    zero = torch.zeros((), dtype=f64, device=dev)
+    parts = [torch.stack([torch.where(valid, v, zero).sum() for v in cols])]
+    if cs:  # summed as summarize sums its [Q, C] columns, so equal counts give equal means
+        parts.append(torch.stack([(torch.where(valid[:, None], m, zero) * w[:, None]).sum(0) for m in per_c]).reshape(-1))
+        names += [f"{name}@{cv}" for name in METRICS for cv in cs]
+    sums = torch.cat(parts + [w.sum().view(1)]).tolist()  # the host read
+    users = int(sums[-1])
+    out = {"users": users}
+    for name, v in zip(names, sums):
+        out[name] = v / users if users else float("nan")
+    return out
+
+
+def evaluate_auc(user_emb: torch.Tensor, item_emb: torch.Tensor, truth, seen=None, users=None, ks=()) -> dict:
+    """Exact full-ranking AUC of an embedding pair: summarize_positions' dict.
+
+    truth, seen and users are evaluate_ranking's: the held-out CSR over all users, the training CSR
+    whose items are left out of every user's ranking, the user indices evaluated (default: every
+    user with a non-empty truth row; pass it to avoid the host read of torch.nonzero's size). Rows of
+    foldin.fold_in serve as user_emb like any others (users = their indices, truth and seen by the
+    same rows). ks: cutoffs for the @c metrics, any positive integers. One rank_positions call (one
+    host read), then summarize_positions (one more)."""
+    _ffi.require_device(user_emb, "evaluate_auc")
+    dev = user_emb.device
+    ptr, idx = truth[0].to(dev), truth[1].to(dev)
+    if users is None:
+        users = torch.nonzero(ptr[1:] > ptr[:-1]).view(-1)
+    users = torch.as_tensor(users).to(device=dev, dtype=torch.int64).view(-1)
+    positions = rank_positions(user_emb, users, item_emb, (ptr, idx), rows=users,
+                               seen=None if seen is None else (seen[0], seen[1], users))
+    return summarize_positions(positions, ks)

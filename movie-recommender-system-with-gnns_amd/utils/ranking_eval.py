@@ -5,6 +5,9 @@ over every user with held-out items, on the HIP path of lgcn_amd.metrics.
     from utils.ranking_eval import evaluate_ranking
     evaluate_ranking(model, train_data.edge_index, test_data.edge_index, 'cuda', ks=(10, 20))
 
+evaluate_auc reports what the cutoffs hide: exact full-ranking AUC, mean percentile rank, MRR and
+mean rank of the held-out items (lgcn_amd.metrics.evaluate_auc), and the @c metrics at any cutoffs.
+
 evaluate_fold_in does the same for users the model never saw: their support items are folded in
 (lgcn_amd.foldin) and left out, their held-out items are the truth.
 """
@@ -40,6 +43,32 @@ def evaluate_ranking(model: torch.nn.Module, train_edge_index: torch.Tensor, hel
         else:
             user_emb, item_emb = model(train_edge_index)
         return metrics.evaluate_ranking(user_emb, item_emb, truth, ks=ks, seen=seen, diversity=diversity, pool=pool)
+
+
+def evaluate_auc(model: torch.nn.Module, train_edge_index: torch.Tensor, heldout_edge_index: torch.Tensor,
+                 device, ks=(), embeddings: str = "raw") -> dict:
+    """Every user with a held-out edge gets the exact position of each held-out item among all items
+    (the items of their training edges left out), and lgcn_amd.metrics.summarize_positions' dict
+    comes back: {'users', 'auc', 'mpr', 'mrr', 'mean_rank'} plus recall / precision / hit_rate /
+    ndcg / mrr at every cutoff of ``ks`` (any positive integers; none by default).
+    Edge sets, ``embeddings`` and the device are evaluate_ranking's."""
+    if embeddings not in ("raw", "propagated"):
+        raise ValueError(f"evaluate_auc: embeddings must be 'raw' or 'propagated', got {embeddings!r}")
+    from lgcn_amd import metrics
+    from lgcn_amd.recommend import seen_csr
+
+    model.eval()
+    U, I = model.num_users, model.num_items
+    with torch.no_grad():
+        train_edge_index = train_edge_index.to(device)
+        seen = seen_csr(train_edge_index, U, I, by="user")
+        truth = seen_csr(heldout_edge_index.to(device), U, I, by="user")
+        if embeddings == "raw":
+            user_emb, item_emb = model.get_embeddings(user_indices=torch.arange(U, device=device),
+                                                      item_indices=torch.arange(I, device=device))
+        else:
+            user_emb, item_emb = model(train_edge_index)
+        return metrics.evaluate_auc(user_emb, item_emb, truth, seen=seen, ks=ks)
 
 
 def evaluate_fold_in(model: torch.nn.Module, train_edge_index: torch.Tensor, support, heldout, device, ks=(20,),

@@ -12,7 +12,9 @@ come in ascending index order. ``recommend_for_users`` serves a batch of users i
 with ``explain=r`` every movie carrying the r movies of the user's history that point at it most
 strongly ('because', lgcn_amd.explain on the device). ``recommend_for_histories`` serves people who
 were not in the training graph from the movies they name (fold-in, lgcn_amd.foldin on the device;
-``python utils/recommend.py --movies 1,296,318``).
+``python utils/recommend.py --movies 1,296,318``). ``rank_for_user`` answers the counterpart of a
+list: where do these movies rank for this user, among all the user could be served (exact positions,
+lgcn_amd.metrics.rank_positions on the device; ``python utils/recommend.py USER_ID --rank 1,296,318``).
 Not carried over: the plotting (``visualizations``) and the import-time seeding (nothing here draws
 random numbers). Unknown ids are answered without touching the GPU; everything else needs the model
 on a ROCm device (lgcn_amd._ffi.LgcnError otherwise, there is no CPU fallback).
@@ -32,6 +34,7 @@ if __name__ == '__main__':  # run as a script: the package root (this file's par
 
 from lgcn_amd import explain as _explain
 from lgcn_amd import foldin as _foldin
+from lgcn_amd import metrics as _metrics
 from lgcn_amd import recommend as _rec
 
 TOP_N = 10  # the reference's list length
@@ -264,6 +267,47 @@ def recommend_for_histories(model: torch.nn.Module, histories: Sequence[Sequence
     return out
 
 
+def rank_for_user(model: torch.nn.Module, user_id: int, movie_ids: Sequence[int], data_handler: Any,
+                  exclude_seen: bool = True, train_edge_index: Optional[torch.Tensor] = None
+                  ) -> Union[Dict[str, str], List[Dict[str, Any]]]:
+    """Where each movie of ``movie_ids`` ranks for the user: one {'movie_id', 'title', 'rank', 'score',
+    'of'} per id, in the order given. 'rank' is 1-based among the 'of' movies the user could be
+    served — rank r is slot r of recommend_for_users' list with the same ``exclude_seen`` /
+    ``train_edge_index`` — and None, like 'score' and 'title' where unknown, for a movie the user has
+    seen (with ``exclude_seen``) or an id the handler does not know. An unknown user gives
+    {'error': 'Invalid user ID'}, answered without touching the GPU. One
+    lgcn_amd.metrics.rank_positions call whatever the number of movies."""
+    user_id_map, movie_id_map = data_handler.user_id_map, data_handler.movie_id_map
+    user_index = user_id_map.get(user_id)
+    if user_index is None:
+        return {'error': 'Invalid user ID'}
+    num_users, num_items = len(user_id_map), len(movie_id_map)
+    title_of = _title_of(data_handler.movies)
+    out = [{'movie_id': m, 'title': title_of.get(m), 'rank': None, 'score': None, 'of': None} for m in movie_ids]
+    known = sorted({movie_id_map[m] - num_users for m in movie_ids if m in movie_id_map})
+    dev = model.user_embedding.weight.device
+    seen = None
+    if exclude_seen:
+        ei = data_handler.edge_index if train_edge_index is None else train_edge_index
+        history = _rec.seen_csr(ei.to(dev), num_users, num_items, by="user")
+        seen = (history[0], history[1], torch.tensor([user_index]))
+    truth = (torch.tensor([0, len(known)], dtype=torch.int64, device=dev),
+             torch.tensor(known, dtype=torch.int32, device=dev))
+    with torch.no_grad():
+        user_emb, item_emb = model.get_embeddings(user_indices=torch.tensor([user_index], device=dev),
+                                                  item_indices=torch.arange(num_items, device=dev))
+        got = _metrics.rank_positions(user_emb, torch.arange(1), item_emb, truth, seen=seen)
+    pos, score, of = got.pos.tolist(), got.score.tolist(), int(got.eligible[0])
+    at = {i: t for t, i in enumerate(known)}
+    for entry in out:
+        entry['of'] = of
+        if entry['movie_id'] in movie_id_map:
+            t = at[movie_id_map[entry['movie_id']] - num_users]
+            if pos[t] >= 0:
+                entry['rank'], entry['score'] = pos[t] + 1, score[t]
+    return out
+
+
 if __name__ == '__main__':
     from data.dataset_handler import MovieLensDataHandler
     from models.light_gcn import LightGCN
@@ -290,6 +334,13 @@ if __name__ == '__main__':
         sys.exit(recommend_from_user(model, uid, handler)['error'])
     train_data, _, _ = handler.get_datasets()
     ei = train_data.edge_index
+    if len(sys.argv) > 3 and sys.argv[2] == '--rank':  # where do these movies rank: USER_ID --rank 1,296,318
+        asked = [int(m) for m in sys.argv[3].split(',') if m.strip()]
+        for r in rank_for_user(model, uid, asked, handler, train_edge_index=ei):
+            where = 'unknown movie' if r['title'] is None else \
+                'already seen' if r['rank'] is None else f"rank {r['rank']} of {r['of']} (Score: {r['score']:.4f})"
+            print(f"{r['movie_id']}: {r['title'] or '?'}: {where}")
+        sys.exit(0)
     seen_items = ei[1, ei[0] == handler.user_id_map[uid]] - handler.num_users
     result = recommend_from_user(model, uid, handler, seen_items)
     why = recommend_for_users(model, [uid], handler, k=TOP_N, train_edge_index=ei, explain=3)[0]
