@@ -8,13 +8,14 @@
 //   k_target_keys   one wave per query: the keys of its truth row's items, 32 per round, and the
 //                   zeroed counts. A round is ONE 32x32 tile of the filter's instruction,
 //                   v_mfma_f32_32x32x2_f32, in the filter's column order, every A row the query and
-//                   B column c the round's c-th item: row 0 of the tile is the 32 scores. The keys
-//                   are therefore the filter's bit for bit — same instruction, same operands, same
-//                   order — and not a restatement of its rounding as an fmaf chain. The tile's other
-//                   31 rows are redundant work, 32 x a few thousand pairs: nothing beside stage b.
-//   k_count_above   the hot path: k_score_filter's tile loop (32 queries per wave in registers,
-//                   32-candidate blocks double-buffered through LDS, the XCD-aware grid) with
-//                   another epilogue. Each of a lane's 16 scores becomes a key and is compared with
+//                   B column c the round's c-th item: row 0 of the tile is the 32 scores
+//                   (ScoreTile::row_keys, defined in lgcn_scoretile.h beside the filter's chain). The
+//                   keys are therefore the filter's bit for bit — same instruction, same operands,
+//                   same order — and not a restatement of its rounding as an fmaf chain. The tile's
+//                   other 31 rows are redundant work, 32 x a few thousand pairs: nothing beside stage b.
+//   k_count_above   the hot path: k_score_filter's tile loop (lgcn_scoretile.h: 32 queries per wave in
+//                   registers, 32-candidate blocks double-buffered through LDS, the XCD-aware grid)
+//                   with another epilogue. Each of a lane's 16 scores becomes a key and is compared with
 //                   TC targets of its query row; the thresholds are read from LDS (the 32 lanes of
 //                   a half-wave share a row: a broadcast), the 16 x TC counters stay in registers.
 //                   At the end of the wave's candidate chunk the counters are summed over the 32
@@ -37,15 +38,11 @@
 // TC (targets per pass) per width, from -Rpass-analysis=kernel-resource-usage: see DESIGN.md §17.
 #include "lgcn_common.h"
 #include "lgcn_ragged.h"
+#include "lgcn_scoretile.h"
 
 using namespace lgcn;
 
 namespace {
-
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-
-// lgcn_recall.hip's score_key: ordered_key with every NaN first (the highest key)
-__device__ __forceinline__ uint32_t score_key(float s) { return s != s ? 0xFFFFFFFFu : ordered_key(s); }
 
 constexpr uint32_t kNoKey = 0u;             // below every score's key (score_key never gives 0)
 constexpr int32_t kNoIndex = 0x7FFFFFFF;    // an index no target is above
@@ -53,30 +50,6 @@ constexpr int32_t kNoIndex = 0x7FFFFFFF;    // an index no target is above
 // i beats j: key above, or the same key and the lower index
 __device__ __forceinline__ int beats(uint32_t ki, int32_t i, uint32_t kj, int32_t j) {
     return (ki > kj) | ((ki == kj) & (i < j));
-}
-
-// The keys of one query against 32 candidates, one per lane pair: lane (i = lane & 31, h = lane >> 5)
-// passes candidate i's index (-1: none, a zero row) and gets candidate i's key. One tile of
-// k_score_filter's chain: step s covers columns s and D/2 + s. Called by whole waves.
-template <int D>
-__device__ __forceinline__ uint32_t row_keys(const float* __restrict__ qrow, const float* __restrict__ Cn,
-                                             int32_t cand, int h) {
-    constexpr int H = D / 2;
-    const float4* a4 = reinterpret_cast<const float4*>(qrow + h * H);
-    const float4* b4 = reinterpret_cast<const float4*>(Cn + static_cast<int64_t>(cand < 0 ? 0 : cand) * D + h * H);
-    f32x16 acc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-#pragma unroll
-    for (int v = 0; v < H / 4; ++v) {
-        const float4 a = a4[v];
-        const float4 b = cand >= 0 ? b4[v] : make_float4(0.f, 0.f, 0.f, 0.f);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, b.x, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, b.y, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, b.z, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, b.w, acc, 0, 0, 0);
-    }
-    return score_key(acc[0]);  // row 4h of the tile, column i: every row is the query
 }
 
 // A fence in the instruction order of k_count_above's epilogue: the row's counters are complete
@@ -112,7 +85,7 @@ __global__ __launch_bounds__(kBlock) void k_target_keys(const float* __restrict_
             const int32_t v = truth_idx[tb + t];
             if (v >= 0 && static_cast<int64_t>(v) < M) j = v;
         }
-        const uint32_t key = row_keys<D>(Qn + q * D, Cn, j, h);
+        const uint32_t key = ScoreTile<D>::row_keys(Qn + q * D, Cn, j, h);
         if (h == 0 && t < n && base + t >= 0 && base + t < nnz) {
             key_out[base + t] = j >= 0 ? key : kNoKey;
             tgt[base + t] = j;
@@ -121,24 +94,16 @@ __global__ __launch_bounds__(kBlock) void k_target_keys(const float* __restrict_
     }
 }
 
-// b. k_score_filter's tile loop with the counting epilogue (see the head of the file, and
-// lgcn_recall.hip for the tiling: a wave's 32 queries in registers, lane (i, h) holding columns
-// h * D/2 + s of query i and of candidate i, candidate blocks double-buffered through LDS, workgroup
-// wid on XCD wid % 8 with the query groups of one candidate chunk on the same XCD).
-template <int D>
-constexpr int count_waves() { return D >= 256 ? 1 : 2; }
-
+// b. the score tile of lgcn_scoretile.h (k_score_filter's, which explains the tiling and the grid)
+// with the counting epilogue: see the head of the file.
 template <int D, int TC>
-__global__ __launch_bounds__(kBlock, count_waves<D>()) void k_count_above(
+__global__ __launch_bounds__(kBlock, ScoreTile<D>::kWaves) void k_count_above(
     const float* __restrict__ Qn, int64_t Q, int32_t nqg, int32_t nchunk, const float* __restrict__ Cn, int64_t M,
     const int64_t* __restrict__ out_ptr, int64_t nnz, const uint32_t* __restrict__ key_out,
     const int32_t* __restrict__ tgt, int32_t* __restrict__ pos_out) {
     static_assert(TC % 4 == 0, "thresholds are read four at a time");
-    constexpr int H = D / 2;
-    constexpr int ROWF = D + 4;
-    constexpr int NF4 = 32 * D / 4;
-    constexpr int PER = (NF4 + kBlock - 1) / kBlock;
-    __shared__ float cs[2][32 * ROWF];
+    using Tile = ScoreTile<D>;
+    __shared__ float cs[2][Tile::kLdsFloats];
     __shared__ __attribute__((aligned(16))) uint32_t s_thr[4][32 * TC];  // [wave][row][target of the pass]
     __shared__ __attribute__((aligned(16))) int32_t s_tgt[4][32 * TC];
     __shared__ int64_t s_base[4][32];
@@ -148,11 +113,9 @@ __global__ __launch_bounds__(kBlock, count_waves<D>()) void k_count_above(
     const int wv = threadIdx.x >> 6;
     const int i = lane & 31;
     const int h = lane >> 5;
-    const int wid = blockIdx.x;
-    const int slot = wid >> 3;
-    const int qg = slot % nqg;
-    const int chunk = (slot / nqg) * 8 + (wid & 7);
-    const int64_t q0 = (int64_t(qg) * 4 + wv) * 32;  // first query of this wave
+    int chunk;
+    int64_t q0;  // first query of this wave
+    Tile::place(nqg, chunk, q0);
     // the truth rows of the workgroup's 128 queries: where their counts are, how many, the longest
     if (threadIdx.x == 0) s_max = 0;
     __syncthreads();
@@ -179,37 +142,9 @@ __global__ __launch_bounds__(kBlock, count_waves<D>()) void k_count_above(
     __syncthreads();
     const int32_t gmax = s_max;  // workgroup-uniform
     if (gmax == 0) return;
-    float a[H];
-    {
-        const float4* src = reinterpret_cast<const float4*>(Qn + (q0 + i) * D + h * H);
-#pragma unroll
-        for (int v = 0; v < H / 4; ++v) {
-            const float4 t = src[v];
-            a[4 * v] = t.x;
-            a[4 * v + 1] = t.y;
-            a[4 * v + 2] = t.z;
-            a[4 * v + 3] = t.w;
-        }
-    }
+    Tile tile;
+    tile.load_queries(Qn, q0);
     const int64_t nblk = (M + 31) / 32;
-    float4 pre[PER];
-    auto fetch = [&](int64_t cb) {
-#pragma unroll
-        for (int p = 0; p < PER; ++p) {
-            const int t = threadIdx.x + p * kBlock;
-            const int r = t / (D / 4), c4 = t % (D / 4);
-            const int64_t j = cb * 32 + r;
-            pre[p] = (t < NF4 && j < M) ? reinterpret_cast<const float4*>(Cn + j * D)[c4]
-                                        : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-    };
-    auto land = [&](int buf) {
-#pragma unroll
-        for (int p = 0; p < PER; ++p) {
-            const int t = threadIdx.x + p * kBlock;
-            if (t < NF4) *reinterpret_cast<float4*>(&cs[buf][(t / (D / 4)) * ROWF + (t % (D / 4)) * 4]) = pre[p];
-        }
-    };
     for (int32_t g0 = 0; g0 < gmax; g0 += TC) {  // a pass: targets g0 .. g0 + TC - 1 of every row
         const bool active = g0 < wmax;  // wave-uniform
         // this wave's thresholds of the pass; a row without a target at a slot gets a key no score
@@ -233,35 +168,17 @@ __global__ __launch_bounds__(kBlock, count_waves<D>()) void k_count_above(
             for (int t = 0; t < TC; ++t) cnt[r][t] = 0;
         int64_t cb = chunk;
         if (cb < nblk) {
-            fetch(cb);
-            land(0);
+            tile.fetch(Cn, M, 1, cb);
+            tile.land(cs, 0);
         }
         __syncthreads();  // also: the thresholds are in place, the previous pass is done with cs
         int buf = 0;
         for (; cb < nblk; cb += nchunk) {
             const int64_t nxt = cb + nchunk;
-            if (nxt < nblk) fetch(nxt);  // in flight during this block's MFMAs
+            if (nxt < nblk) tile.fetch(Cn, M, 1, nxt);  // in flight during this block's MFMAs
             if (active) {
-                f32x16 acc;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-                const float* brow = &cs[buf][i * ROWF + h * H];
-                constexpr int G = (H / 4) >= 4 ? 4 : (H / 4);
-#pragma unroll
-                for (int v0 = 0; v0 < H / 4; v0 += G) {
-                    float4 bv[G];
-#pragma unroll
-                    for (int g = 0; g < G; ++g) bv[g] = *reinterpret_cast<const float4*>(brow + 4 * (v0 + g));
-#pragma unroll
-                    for (int g = 0; g < G; ++g) {
-                        const int v = v0 + g;
-                        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[4 * v], bv[g].x, acc, 0, 0, 0);
-                        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[4 * v + 1], bv[g].y, acc, 0, 0, 0);
-                        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[4 * v + 2], bv[g].z, acc, 0, 0, 0);
-                        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[4 * v + 3], bv[g].w, acc, 0, 0, 0);
-                    }
-                }
-                // epilogue: column = candidate j (this lane's), rows = queries (r&3) + 8*(r>>2) + 4h
+                const f32x16 acc = tile.scores(cs, buf);
+                // epilogue: column = candidate j (this lane's), rows = queries Tile::row(r, h)
                 const int64_t j = cb * 32 + i;
                 const int32_t jj = static_cast<int32_t>(j);
                 const uint32_t jmask = j < M ? 0xFFFFFFFFu : kNoKey;  // a candidate past M has no key
@@ -277,7 +194,7 @@ __global__ __launch_bounds__(kBlock, count_waves<D>()) void k_count_above(
                     const uint32_t key = score_key(acc[r]) & jmask;
                     uint4 nx[TC / 4];
                     if (r < 15) {
-                        const int row0 = ((r + 1) & 3) + 8 * ((r + 1) >> 2);
+                        const int row0 = Tile::row(r + 1, 0);  // tp is at row 4h
 #pragma unroll
                         for (int t4 = 0; t4 < TC / 4; ++t4) nx[t4] = tp[row0 * (TC / 4) + t4];
                     }
@@ -301,7 +218,7 @@ __global__ __launch_bounds__(kBlock, count_waves<D>()) void k_count_above(
                     asm volatile("" ::: "memory");
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
-                        const int row = (r & 3) + 8 * (r >> 2) + 4 * h;
+                        const int row = Tile::row(r, h);
                         const uint32_t key = score_key(acc[r]) & jmask;
 #pragma unroll
                         for (int t = 0; t < TC; ++t)
@@ -310,7 +227,7 @@ __global__ __launch_bounds__(kBlock, count_waves<D>()) void k_count_above(
                     }
                 }
             }
-            if (nxt < nblk) land(buf ^ 1);
+            if (nxt < nblk) tile.land(cs, buf ^ 1);
             __syncthreads();
             buf ^= 1;
         }
@@ -318,7 +235,7 @@ __global__ __launch_bounds__(kBlock, count_waves<D>()) void k_count_above(
             // sum each counter over the 32 lanes of its row, one atomic per (query, target)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int row = (r & 3) + 8 * (r >> 2) + 4 * h;
+                const int row = Tile::row(r, h);
                 const int32_t len = s_len[wv][row];
                 const int64_t base = s_base[wv][row];
 #pragma unroll
@@ -376,7 +293,7 @@ __device__ __forceinline__ void finish_query(uint2* ent, int64_t q, const float*
                 const int32_t v = seen[e0 + i];
                 if (v >= 0 && static_cast<int64_t>(v) < M) cand = v;
             }
-            const uint32_t key = row_keys<D>(Qn + q * D, Cn, cand, h);
+            const uint32_t key = ScoreTile<D>::row_keys(Qn + q * D, Cn, cand, h);
             if (h == 0)
                 ent[wv * kFinishChunk + rd * 32 + i] =
                     cand >= 0 ? make_uint2(key, static_cast<uint32_t>(cand)) : make_uint2(kNoKey, kNoIndex);
@@ -467,7 +384,6 @@ template <int D>
 int launch_positions(const float* Qn, int64_t Qpad, int64_t Q, const float* Cn, int64_t M, const int64_t* truth_ptr,
                      const int32_t* truth_idx, const int64_t* truth_row, int64_t truth_rows, const FinishArgs& F,
                      uint32_t* key_out, int32_t* tgt, int32_t stages, hipStream_t s) {
-    constexpr int QW = 4 * 32;  // queries per workgroup of the dense count
     int rc = LGCN_OK;
     if (stages & LGCN_RANKPOS_KEYS) {
         k_target_keys<D><<<grid_for(Q * 64, kBlock, int64_t(1) << 31), kBlock, 0, s>>>(
@@ -476,18 +392,14 @@ int launch_positions(const float* Qn, int64_t Qpad, int64_t Q, const float* Cn, 
         if (rc != LGCN_OK) return rc;
     }
     if (M > 0 && (stages & LGCN_RANKPOS_COUNT)) {
-        const int64_t nblk = (M + 31) / 32;
-        const int64_t nqg = (Q + QW - 1) / QW;  // query groups that hold a real query (<= Qpad / QW)
-        // candidate chunks: a multiple of 8 (the XCD mapping), ~2048 workgroups in all
-        int64_t nchunk = (2048 / nqg + 7) / 8 * 8;
-        const int64_t need = (nblk + 7) / 8 * 8;
-        if (nchunk > need) nchunk = need;
-        if (nchunk < 8) nchunk = 8;
-        const int64_t grid = nqg * nchunk;
-        if (grid > INT32_MAX) return fail(LGCN_E_ARG, "lgcn_rank_positions: too many queries for one launch");
-        k_count_above<D, count_targets<D>()><<<dim3(static_cast<unsigned>(grid)), kBlock, 0, s>>>(
-            Qn, Q, static_cast<int32_t>(nqg), static_cast<int32_t>(nchunk), Cn, M, F.out_ptr, F.nnz, key_out, tgt,
-            F.pos_out);
+        // query groups that hold a real query (<= Qpad / kTileQueries)
+        const int64_t nqg = (Q + kTileQueries - 1) / kTileQueries;
+        int32_t nchunk;
+        unsigned grid;
+        if (!score_grid(nqg, M, nchunk, grid))
+            return fail(LGCN_E_ARG, "lgcn_rank_positions: too many queries for one launch");
+        k_count_above<D, count_targets<D>()><<<dim3(grid), kBlock, 0, s>>>(
+            Qn, Q, static_cast<int32_t>(nqg), nchunk, Cn, M, F.out_ptr, F.nnz, key_out, tgt, F.pos_out);
         rc = check_launch("k_count_above");
         if (rc != LGCN_OK) return rc;
     }

@@ -8,8 +8,9 @@
 //   k_normalize_rows  x[r] / ||x[r]|| (optionally gathered through an index list), written into a
 //                     zero-padded [rows, D] image (D = the compiled width >= d);
 //   k_score_filter    f32 MFMA (v_mfma_f32_32x32x2_f32, exact f32) scores of 32-query blocks
-//                     against 32-candidate blocks; an epilogue keeps (key, index) of every score
-//                     at or above the query's threshold key in a per-query list;
+//                     against 32-candidate blocks (the tile of lgcn_scoretile.h); an epilogue keeps
+//                     (key, index) of every score at or above the query's threshold key in a
+//                     per-query list;
 //   k_select_topk     one workgroup per query: radix select (4 x 8-bit passes) of the k-th
 //                     largest key in its list, then either that key (a new threshold) or the
 //                     hit count (positives above it, plus positives among the ties);
@@ -29,18 +30,11 @@
 
 #include "lgcn_common.h"
 #include "lgcn_ragged.h"
+#include "lgcn_scoretile.h"
 
 using namespace lgcn;
 
 namespace {
-
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-
-// ordered_key with every NaN first (the highest key)
-__device__ __forceinline__ uint32_t score_key(float s) { return s != s ? 0xFFFFFFFFu : ordered_key(s); }
-
-// inverse of score_key (the NaN key maps back to a NaN)
-__device__ __forceinline__ float key_score(uint32_t k) { return ordered_value(k); }
 
 // one 32-lane half-wave per row
 __global__ __launch_bounds__(kBlock) void k_normalize_rows(const float* __restrict__ x, const int64_t* __restrict__ idx,
@@ -68,33 +62,16 @@ __global__ __launch_bounds__(kBlock) void k_normalize_rows(const float* __restri
 
 constexpr int kStage = 512;  // staged accepted scores per wave
 
-// Workgroup = 4 waves over the same candidate blocks; wave w owns the 32 queries
-// [(qg*4 + w)*32, +32), held in registers for the whole launch. Lane l = (i = l&31, h = l>>5)
-// holds, for MFMA step s, A = Q[i][h*D/2 + s] and B = C[j][h*D/2 + s], so each step's 2-wide k
-// slice is columns s and D/2+s and the D/2 steps cover the row.
-// Candidate blocks (32 rows) are staged through LDS, double-buffered: the global loads of block
-// n+1 are in flight (in registers) while block n's MFMAs run, and land in the other buffer.
-// Grid: 1-D, XCD-aware. Workgroup wid runs on XCD wid % 8; the query groups of one candidate
-// chunk get consecutive slots of the SAME XCD, so they run together and share its L2 copy of the
-// chunk's rows (the queries, not the candidates, are what differs between them).
-// At <= 170 VGPRs two waves share each SIMD, so one wave's epilogue hides under the other's MFMAs.
-// D = 256 asks for one: its two candidate buffers + staging (≈ 89 KB of LDS per workgroup) leave
-// room for one workgroup (one wave per SIMD) per CU whatever the register count.
+// The score tile of lgcn_scoretile.h (which explains the tiling, the grid and the occupancy) with
+// the filtering epilogue: the thresholds of a lane's 16 query rows in registers, accepted scores
+// staged per wave in LDS.
 template <int D>
-constexpr int score_filter_waves() { return D >= 256 ? 1 : 2; }
-
-template <int D>
-__global__ __launch_bounds__(kBlock, score_filter_waves<D>()) void k_score_filter(const float* __restrict__ Qn, int64_t Qvalid, int32_t nqg,
-                                                            int32_t nchunk, const float* __restrict__ Cn, int64_t M,
-                                                            int64_t stride, const uint32_t* __restrict__ thr,
-                                                            uint32_t* __restrict__ list_key,
-                                                            int32_t* __restrict__ list_idx,
-                                                            int32_t* __restrict__ list_n, int32_t cap) {
-    constexpr int H = D / 2;
-    constexpr int ROWF = D + 4;               // padded LDS row: conflict-free ds_read_b128 down a column
-    constexpr int NF4 = 32 * D / 4;           // float4s per candidate block
-    constexpr int PER = (NF4 + kBlock - 1) / kBlock;
-    __shared__ float cs[2][32 * ROWF];
+__global__ __launch_bounds__(kBlock, ScoreTile<D>::kWaves) void k_score_filter(
+    const float* __restrict__ Qn, int64_t Qvalid, int32_t nqg, int32_t nchunk, const float* __restrict__ Cn, int64_t M,
+    int64_t stride, const uint32_t* __restrict__ thr, uint32_t* __restrict__ list_key, int32_t* __restrict__ list_idx,
+    int32_t* __restrict__ list_n, int32_t cap) {
+    using Tile = ScoreTile<D>;
+    __shared__ float cs[2][Tile::kLdsFloats];
     // wave-private staging of accepted scores: appended without atomics (ballot prefix), flushed
     // to the per-query lists with ONE returning global atomic per query per flush
     __shared__ uint32_t st_key[4][kStage];
@@ -107,31 +84,19 @@ __global__ __launch_bounds__(kBlock, score_filter_waves<D>()) void k_score_filte
     const int wv = threadIdx.x >> 6;
     const int i = lane & 31;
     const int h = lane >> 5;
-    const int wid = blockIdx.x;
-    const int slot = wid >> 3;
-    const int qg = slot % nqg;
-    const int chunk = (slot / nqg) * 8 + (wid & 7);
-    const int64_t q0 = (int64_t(qg) * 4 + wv) * 32;  // first query of this wave
-    float a[H];
-    {
-        const float4* src = reinterpret_cast<const float4*>(Qn + (q0 + i) * D + h * H);
-#pragma unroll
-        for (int v = 0; v < H / 4; ++v) {
-            const float4 t = src[v];
-            a[4 * v] = t.x;
-            a[4 * v + 1] = t.y;
-            a[4 * v + 2] = t.z;
-            a[4 * v + 3] = t.w;
-        }
-    }
-    // this lane's 16 output rows: (r&3) + 8*(r>>2) + 4h. The test runs on floats, inclusively:
+    int chunk;
+    int64_t q0;  // first query of this wave
+    Tile::place(nqg, chunk, q0);
+    Tile tile;
+    tile.load_queries(Qn, q0);
+    // this lane's 16 output rows. The test runs on floats, inclusively:
     // !(score < t) keeps every score whose key is >= the threshold key (and NaN, which ranks
     // first, and -0 beside +0 — extra entries are harmless, the selection works on exact keys).
     // Padding queries get +inf (their zero rows score 0).
     float th[16];
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-        const int64_t q = q0 + (r & 3) + 8 * (r >> 2) + 4 * h;
+        const int64_t q = q0 + Tile::row(r, h);
         th[r] = (q < Qvalid) ? (thr ? key_score(thr[q]) : -__builtin_inff()) : __builtin_inff();
     }
     int scnt = 0;  // wave-uniform staged count
@@ -162,54 +127,17 @@ __global__ __launch_bounds__(kBlock, score_filter_waves<D>()) void k_score_filte
         scnt = 0;
     };
     const int64_t nblk = (M + 31) / 32;
-    float4 pre[PER];
-    auto fetch = [&](int64_t cb) {
-#pragma unroll
-        for (int p = 0; p < PER; ++p) {
-            const int t = threadIdx.x + p * kBlock;
-            const int r = t / (D / 4), c4 = t % (D / 4);
-            const int64_t j = cb * 32 + r;
-            pre[p] = (t < NF4 && j < M) ? reinterpret_cast<const float4*>(Cn + j * stride * D)[c4]
-                                        : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-    };
-    auto land = [&](int buf) {
-#pragma unroll
-        for (int p = 0; p < PER; ++p) {
-            const int t = threadIdx.x + p * kBlock;
-            if (t < NF4) *reinterpret_cast<float4*>(&cs[buf][(t / (D / 4)) * ROWF + (t % (D / 4)) * 4]) = pre[p];
-        }
-    };
     int64_t cb = chunk;
     if (cb < nblk) {
-        fetch(cb);
-        land(0);
+        tile.fetch(Cn, M, stride, cb);
+        tile.land(cs, 0);
     }
     __syncthreads();
     int buf = 0;
     for (; cb < nblk; cb += nchunk) {
         const int64_t nxt = cb + nchunk;
-        if (nxt < nblk) fetch(nxt);  // in flight during this block's MFMAs
-        f32x16 acc;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-        const float* brow = &cs[buf][i * ROWF + h * H];
-        // B in groups of G float4 per LDS wait (G*4 MFMAs behind each wait)
-        constexpr int G = (H / 4) >= 4 ? 4 : (H / 4);
-#pragma unroll
-        for (int v0 = 0; v0 < H / 4; v0 += G) {
-            float4 bv[G];
-#pragma unroll
-            for (int g = 0; g < G; ++g) bv[g] = *reinterpret_cast<const float4*>(brow + 4 * (v0 + g));
-#pragma unroll
-            for (int g = 0; g < G; ++g) {
-                const int v = v0 + g;
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[4 * v], bv[g].x, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[4 * v + 1], bv[g].y, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[4 * v + 2], bv[g].z, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[4 * v + 3], bv[g].w, acc, 0, 0, 0);
-            }
-        }
+        if (nxt < nblk) tile.fetch(Cn, M, stride, nxt);  // in flight during this block's MFMAs
+        const f32x16 acc = tile.scores(cs, buf);
         // epilogue: column = candidate j (this lane's), rows = queries; branch-free test, and
         // a wave-uniform branch only for the (rare) slots where some lane passes
         const int64_t j = cb * 32 + i;
@@ -217,8 +145,7 @@ __global__ __launch_bounds__(kBlock, score_filter_waves<D>()) void k_score_filte
         const bool jok = j < M;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int row0 = (r & 3) + 8 * (r >> 2);
-            const int row = row0 + 4 * h;
+            const int row = Tile::row(r, h);
             const bool take = jok & !(acc[r] < th[r]);
             if (thr == nullptr) {  // dense mode: every subset score at its subset slot
                 const uint32_t key = score_key(acc[r]);
@@ -241,7 +168,7 @@ __global__ __launch_bounds__(kBlock, score_filter_waves<D>()) void k_score_filte
             }
             scnt += n;
         }
-        if (nxt < nblk) land(buf ^ 1);
+        if (nxt < nblk) tile.land(cs, buf ^ 1);
         __syncthreads();
         buf ^= 1;
     }
@@ -743,20 +670,15 @@ __global__ __launch_bounds__(64) void k_select_stl_nth(uint32_t* __restrict__ li
 template <int D>
 int launch_filter(const float* Qn, int64_t Qpad, int64_t Qvalid, const float* Cn, int64_t M, int64_t stride,
                   const uint32_t* thr, uint32_t* lk, int32_t* li, int32_t* ln, int32_t cap, hipStream_t s) {
-    constexpr int QW = 4 * 32;  // queries per workgroup
-    if (Qpad % QW != 0) return fail(LGCN_E_ARG, "lgcn_score_filter: padded query count %lld not a multiple of %d",
-                                    (long long)Qpad, QW);
-    const int64_t nblk = (M + 31) / 32;
-    const int64_t nqg = Qpad / QW;
-    // candidate chunks: a multiple of 8 (the XCD mapping), ~2048 workgroups in all
-    int64_t nchunk = (2048 / nqg + 7) / 8 * 8;
-    const int64_t need = (nblk + 7) / 8 * 8;
-    if (nchunk > need) nchunk = need;
-    if (nchunk < 8) nchunk = 8;
-    const int64_t grid = nqg * nchunk;
-    if (grid > INT32_MAX || nqg > INT32_MAX) return fail(LGCN_E_ARG, "lgcn_score_filter: too many queries");
-    k_score_filter<D><<<dim3(static_cast<unsigned>(grid)), kBlock, 0, s>>>(
-        Qn, Qvalid, static_cast<int32_t>(nqg), static_cast<int32_t>(nchunk), Cn, M, stride, thr, lk, li, ln, cap);
+    if (Qpad % kTileQueries != 0)
+        return fail(LGCN_E_ARG, "lgcn_score_filter: padded query count %lld not a multiple of %d", (long long)Qpad,
+                    kTileQueries);
+    const int64_t nqg = Qpad / kTileQueries;
+    int32_t nchunk;
+    unsigned grid;
+    if (!score_grid(nqg, M, nchunk, grid)) return fail(LGCN_E_ARG, "lgcn_score_filter: too many queries");
+    k_score_filter<D><<<dim3(grid), kBlock, 0, s>>>(Qn, Qvalid, static_cast<int32_t>(nqg), nchunk, Cn, M, stride, thr, lk,
+                                                    li, ln, cap);
     return check_launch("k_score_filter");
 }
 

@@ -247,7 +247,7 @@ INCLUDE = _HERE.parent.parent / "include"
 SOURCES = ("lgcn_plan.hip", "lgcn_spmm.hip", "lgcn_optim.hip", "lgcn_bpr.hip", "lgcn_recall.hip", "lgcn_metrics.hip", "lgcn_rerank.hip",
            "lgcn_explain.hip", "lgcn_foldin.hip", "lgcn_negatives.hip", "lgcn_rankpos.hip", "lgcn_rowadam.hip", "lgcn_exchange.hip", "lgcn_partition.cpp", "lgcn_sample.cpp", "lgcn_tuning.cpp", "lgcn_program.cpp")
 # the headers they include (csrc/), hashed and tracked as build dependencies with include/lgcn.h
-HEADERS = ("lgcn_common.h", "lgcn_exact.h", "lgcn_reg.h", "lgcn_ragged.h")
+HEADERS = ("lgcn_common.h", "lgcn_exact.h", "lgcn_reg.h", "lgcn_ragged.h", "lgcn_scoretile.h")
 
 
 def source_sha256() -> str:

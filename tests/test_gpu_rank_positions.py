@@ -15,8 +15,11 @@ from rank_position_checker import key_scores, positions_from_keys, summaries64
 pytestmark = pytest.mark.gpu
 
 # (d, Q, M): padded widths (8 -> 8, 48 -> 64), padded and several query groups, M no multiple of 32,
-# several candidate chunks; d = 128 is the width that takes 4 targets per pass, the others take 8
-SHAPES = [(8, 5, 33), (64, 70, 100), (48, 130, 1000), (128, 33, 257), (256, 20, 300), (64, 200, 5000)]
+# several candidate chunks; d = 128 is the width that takes 4 targets per pass, the others take 8.
+# (16, 40, 70) and (24, 40, 70) run the compiled widths 16 and 32 (24 pads to 32): two waves of one
+# workgroup with padding queries, three candidate blocks with the last one partial
+SHAPES = [(8, 5, 33), (64, 70, 100), (48, 130, 1000), (128, 33, 257), (256, 20, 300), (64, 200, 5000),
+          (16, 40, 70), (24, 40, 70)]
 TRUTH_LENGTHS = (0, 1, 5, 4, 8, 9, 40)  # none, one, a few, Tc and Tc + 1 of either kind, several passes
 
 

@@ -29,7 +29,7 @@ def _check_hits(gpu, users, pos, neg, picked, k, **kw):
     return hits, ref
 
 
-@pytest.mark.parametrize("d", [8, 32, 64, 100, 128, 256])
+@pytest.mark.parametrize("d", [8, 16, 32, 64, 100, 128, 256])
 @pytest.mark.parametrize("k", [1, 20, 100])
 def test_topk_hits_match_oracle(gpu, d, k):
     rng = np.random.default_rng(d * 1000 + k)

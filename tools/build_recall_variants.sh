@@ -1,34 +1,40 @@
 #!/bin/bash
 # Builds k_score_filter A/B variants of liblgcn.so into tools/_variants/ (see tools/recall_variants.py).
-# The variants are not in the product source: each is spliced into a copy of lgcn_recall.hip here
-# (NO_MFMA: the MFMA chain replaced by one multiply per accumulator; NO_EPI: the epilogue skipped).
+# The variants are not in the product source: each is spliced into a copy of the sources here
+# (NO_MFMA: the MFMA chain of lgcn_scoretile.h's ScoreTile::scores replaced by one multiply per
+# accumulator; NO_EPI: k_score_filter's epilogue in lgcn_recall.hip skipped).
 set -e
 R=$(cd "$(dirname "$0")/.." && pwd)
 C=$R/movie-recommender-system-with-gnns_amd/csrc
 T=$R/tools/_variants
 mkdir -p "$T/src"
 cp "$C"/*.hip "$C"/*.cpp "$C"/*.h "$T/src/"
-python3 - "$T/src/lgcn_recall.hip" <<'EOF'
+python3 - "$T/src" <<'EOF'
 import sys
-p = sys.argv[1]
-s = open(p).read()
-mfma = "        constexpr int G = (H / 4) >= 4 ? 4 : (H / 4);\n"
-epi = "        // epilogue: column = candidate j (this lane's), rows = queries; branch-free test, and\n"
-assert mfma in s and epi in s
-s = s.replace(mfma, mfma + """#ifdef LGCN_VARIANT_NO_MFMA
+d = sys.argv[1]
+
+
+def splice(name, at, text, before):
+    s = open(f"{d}/{name}").read()
+    assert s.count(at) == 1, (name, at)
+    open(f"{d}/{name}", "w").write(s.replace(at, text + at if before else at + text))
+
+
+splice("lgcn_scoretile.h", "        constexpr int G = (H / 4) >= 4 ? 4 : (H / 4);\n", """#ifdef LGCN_VARIANT_NO_MFMA
         for (int r = 0; r < 16; ++r) acc[r] = brow[r] * a[r];
         if (false)
 #endif
-""", 1)
-s = s.replace(epi, """#ifdef LGCN_VARIANT_NO_EPI
+""", before=False)
+splice("lgcn_recall.hip",
+       "        // epilogue: column = candidate j (this lane's), rows = queries; branch-free test, and\n",
+       """#ifdef LGCN_VARIANT_NO_EPI
         if (acc[0] == 12345.f && acc[15] == 54321.f) list_n[0] = 1;  // keep acc live; never true
-        if (nxt < nblk) land(buf ^ 1);
+        if (nxt < nblk) tile.land(cs, buf ^ 1);
         __syncthreads();
         buf ^= 1;
         continue;
 #endif
-""" + epi, 1)
-open(p, "w").write(s)
+""", before=True)
 EOF
 # the tree's provenance hash (as tools/build_variant.py links it), so lgcn_amd._ffi loads the variant
 SHA=$(cd "$R" && python3 -c "import __graft_entry__ as g; print(g._ffi_module().source_sha256())")
