@@ -651,6 +651,36 @@ int lgcn_select_topk_ranked(const uint32_t* list_key, const int32_t* list_idx, c
                             const int32_t* excl_idx, const int64_t* excl_row, int64_t excl_rows, uint32_t* thr_out,
                             int32_t* out_idx, float* out_score, int32_t* out_n, lgcn_stream_t stream);
 
+/* Attribute-filtered top-k (added under ABI 11, purely additive): "ten comedies", "anything but
+ * horror", "only what is in the catalogue tonight", tested where the score is tested, so a list only
+ * ever holds candidates that pass.
+ *   attr[j]: the 32-bit attribute word of candidate row j (indexed by the candidate index a list
+ *     entry carries, so by r * stride in lgcn_score_filter_attr).
+ *   where[q * 3 + 0..2]: query q's masks (any, all, none), rows [0, Qvalid); the rows of padding
+ *     queries are not read.
+ *   Candidate j passes for query q when all three hold:
+ *       (attr[j] & none) == 0,   (attr[j] & all) == all,   any == 0 || (attr[j] & any) != 0.
+ *     (0, 0, 0) passes everything; attr == 0 passes only filters with any == 0 and all == 0.
+ *   A candidate is eligible when it passes and is not in the query's exclusion row. Everything else
+ *   is the unfiltered entry point's contract: the keys, the ranking rule (key descending, index
+ *   ascending, NaN first), the -1 / -inf slots of a short list, the padding queries, the limits.
+ * lgcn_select_topk_ranked_attr: lgcn_select_topk_ranked whose eligibility also requires the
+ *   predicate. On dense rows it alone makes the result exact; in threshold mode over a candidate
+ *   subset the threshold is the k-th best of a subset of the eligible candidates, hence still a
+ *   lower bound (0, "accept everything", when fewer than k subset entries are eligible).
+ * lgcn_score_filter_attr: lgcn_score_filter in list mode only (thr and list_n required; thr NULL is
+ *   LGCN_E_ARG, dense rows stay with lgcn_score_filter): a key >= thr[q] is appended only if its
+ *   candidate passes, so under thr[q] = 0 query q's list is every passing candidate. No workspace.
+ * attr or where NULL is LGCN_E_ARG in both. */
+int lgcn_score_filter_attr(const float* Qn, int64_t Qpad, int64_t Qvalid, const float* Cn, int64_t M, int64_t stride,
+                           int32_t D, const uint32_t* thr, uint32_t* list_key, int32_t* list_idx, int32_t* list_n,
+                           int32_t cap, const uint32_t* attr, const uint32_t* where, lgcn_stream_t stream);
+int lgcn_select_topk_ranked_attr(const uint32_t* list_key, const int32_t* list_idx, const int32_t* list_n,
+                                 int32_t dense_n, int32_t cap, int32_t k, int64_t Qpad, int64_t Qvalid,
+                                 const int64_t* excl_ptr, const int32_t* excl_idx, const int64_t* excl_row,
+                                 int64_t excl_rows, uint32_t* thr_out, int32_t* out_idx, float* out_score,
+                                 int32_t* out_n, const uint32_t* attr, const uint32_t* where, lgcn_stream_t stream);
+
 /* Full-ranking evaluation counts (added under ABI 11, purely additive): ranked lists plus held-out
  * sets in, what Recall / Precision / HitRate / NDCG / MRR at several cutoffs are made of out, in
  * one pass and without leaving the device (one wave per query).

@@ -112,7 +112,8 @@ class MovieLensDataHandler:
             download_and_extract_dataset()
         ratings = pd.read_csv(ratings_path, usecols=["userId", "movieId", "rating"])
         ratings = ratings[ratings["rating"] >= min_rating]
-        self.movies = pd.read_csv(movies_path, usecols=["movieId", "title"])
+        # genres (where the file has the column) feeds utils.recommend.genre_table's attribute words
+        self.movies = pd.read_csv(movies_path, usecols=lambda c: c in ("movieId", "title", "genres"))
         # ids in order of first appearance == enumerate(series.unique()) of the reference
         user_codes, user_ids = pd.factorize(ratings["userId"], sort=False)
         movie_codes, movie_ids = pd.factorize(ratings["movieId"], sort=False)

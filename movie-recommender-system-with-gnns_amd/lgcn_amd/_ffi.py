@@ -144,6 +144,10 @@ _SIGS = {
     "lgcn_select_topk_stl": ([_vp, _vp, _i64, _i64, _i32, _i64, _i64, _i64, _vp, _vp], ctypes.c_int),
     "lgcn_select_topk_ranked": ([_vp, _vp, _vp, _i32, _i32, _i32, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp,
                                  _vp], ctypes.c_int),
+    "lgcn_score_filter_attr": ([_vp, _i64, _i64, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp],
+                               ctypes.c_int),
+    "lgcn_select_topk_ranked_attr": ([_vp, _vp, _vp, _i32, _i32, _i32, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp,
+                                      _vp, _vp, _vp, _vp], ctypes.c_int),
     "lgcn_rank_metrics": ([_vp, _i64, _i32, _i64, _vp, _vp, _vp, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _vp], ctypes.c_int),
     "lgcn_rerank_mmr": ([_vp, _vp, _i64, _i32, _i64, _vp, _i64, _i32, _i32, _f32, _vp, _vp, _vp, _vp, _vp], ctypes.c_int),
     "lgcn_explain_topr": ([_vp, _i64, _i32, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp,
@@ -244,10 +248,10 @@ def load(path: os.PathLike | str | None = None) -> ctypes.CDLL:
 CSRC = _HERE.parent / "csrc"
 INCLUDE = _HERE.parent.parent / "include"
 # the translation units of liblgcn.so (lgcn_build.cpp carries the hash and is not hashed)
-SOURCES = ("lgcn_plan.hip", "lgcn_spmm.hip", "lgcn_optim.hip", "lgcn_bpr.hip", "lgcn_recall.hip", "lgcn_metrics.hip", "lgcn_rerank.hip",
+SOURCES = ("lgcn_plan.hip", "lgcn_spmm.hip", "lgcn_optim.hip", "lgcn_bpr.hip", "lgcn_recall.hip", "lgcn_recall_attr.hip", "lgcn_metrics.hip", "lgcn_rerank.hip",
            "lgcn_explain.hip", "lgcn_foldin.hip", "lgcn_negatives.hip", "lgcn_rankpos.hip", "lgcn_rowadam.hip", "lgcn_exchange.hip", "lgcn_partition.cpp", "lgcn_sample.cpp", "lgcn_tuning.cpp", "lgcn_program.cpp")
 # the headers they include (csrc/), hashed and tracked as build dependencies with include/lgcn.h
-HEADERS = ("lgcn_common.h", "lgcn_exact.h", "lgcn_reg.h", "lgcn_ragged.h", "lgcn_scoretile.h")
+HEADERS = ("lgcn_common.h", "lgcn_exact.h", "lgcn_reg.h", "lgcn_ragged.h", "lgcn_scoretile.h", "lgcn_recall_lists.h")
 
 
 def source_sha256() -> str:

@@ -154,7 +154,8 @@ def evaluate_ranking(user_emb: torch.Tensor, item_emb: torch.Tensor, truth, ks=(
     truth: the held-out CSR over all users, (ptr, idx) as recommend.seen_csr(heldout_edges, U, I)
     builds it; seen: the training CSR whose items are left out of every user's ranking (None:
     nothing excluded); users: the user indices evaluated (default: every user with a non-empty
-    truth row); ks: the cutoffs; topk_kw: recommend.topk_rows' cap / subset.
+    truth row); ks: the cutoffs; topk_kw: recommend.topk_rows' cap / subset / attrs / where (an attribute
+    filter: the metrics of the filtered lists against the same truth).
     One recommend.topk_items call for max(ks) items per user, one lgcn_rank_metrics launch, then
     summarize. Host reads: summarize's one; topk_rows' one per query block when the items exceed
     its dense capacity; and, when ``users`` is left to default, the size of torch.nonzero's result

@@ -12,6 +12,10 @@ any point and the host reads at most one value pair per query block.
                                          lgcn_score_filter (dense) + lgcn_select_topk_ranked (threshold)
                  lists = scores >= thr   lgcn_score_filter (f32 MFMA, all M)
                  ranked emit             lgcn_select_topk_ranked
+    with attrs= / where= (an attribute filter per query: "ten comedies", "anything but horror") the
+    ranked selections are lgcn_select_topk_ranked_attr and the lists lgcn_score_filter_attr's, which
+    test a candidate's attribute word where they test its score: a list only ever holds candidates
+    that pass, so a filter that passes 0.5 % of the items costs no capacity.
 
 Ranking rule: score descending, then candidate index ascending (NaN scores first). The threshold
 is formed from eligible subset entries only: it is then the k-th best of a subset of the eligible
@@ -26,6 +30,7 @@ Diversity on top of relevance (csrc/lgcn_rerank.hip, one wave per query, the poo
 from __future__ import annotations
 
 import ctypes
+import operator
 from typing import NamedTuple
 
 import torch
@@ -83,8 +88,80 @@ def _excl_args(excl, dev, Q: int):
     return ptr.to(dev).contiguous(), idx.to(dev).contiguous(), rows, ptr.numel() - 1
 
 
+def attr_bits(labels, vocabulary) -> torch.Tensor:
+    """The attribute words of ``attrs=``: int32 [rows] on the CPU, bit b of row r set when
+    ``vocabulary[b]`` is among ``labels[r]`` (a collection of labels per row; an empty one gives 0).
+    At most 32 labels (bit 31 is the int32's sign bit); a label outside the vocabulary is a
+    ValueError naming it."""
+    vocabulary = list(vocabulary)
+    if len(vocabulary) > 32:
+        raise ValueError(f"attr_bits: {len(vocabulary)} labels, an attribute word holds 32")
+    bit = {v: b for b, v in enumerate(vocabulary)}
+    if len(bit) != len(vocabulary):
+        raise ValueError("attr_bits: the vocabulary names a label twice")
+    words = []
+    for r, row in enumerate(labels):
+        w = 0
+        for label in row:
+            if label not in bit:
+                raise ValueError(f"attr_bits: row {r} carries {label!r}, which is not in the vocabulary {vocabulary}")
+            w |= 1 << bit[label]
+        words.append(w - (1 << 32) if w >= 1 << 31 else w)
+    return torch.tensor(words, dtype=torch.int32)
+
+
+def _mask_column(name: str, m, Q: int) -> torch.Tensor:
+    """One member of ``where`` as int64 [Q] or [1] values in [-2**31, 2**31): ints of [0, 2**32) are
+    taken as the uint32 bit pattern."""
+    if m is None:
+        m = 0
+    if isinstance(m, bool) or (isinstance(m, torch.Tensor) and (m.dtype == torch.bool or m.is_floating_point()
+                                                                 or m.is_complex())):
+        raise TypeError(f"recommend: where's {name} mask must be an int or integers, got {m!r}")
+    if isinstance(m, int):
+        if not -(1 << 31) <= m < 1 << 32:
+            raise ValueError(f"recommend: where's {name} mask {m} is outside 32 bits")
+        t = torch.tensor([m], dtype=torch.int64)
+    elif isinstance(m, torch.Tensor) and m.dtype in (torch.int32, torch.int16, torch.int8, torch.uint8):
+        if m.numel() != Q:
+            raise ValueError(f"recommend: where's {name} mask has {m.numel()} entries for {Q} queries")
+        return m.detach().to(torch.int64).reshape(-1)  # in range as it is: nothing to read back
+    else:
+        try:
+            t = m.detach().to(torch.int64).reshape(-1) if isinstance(m, torch.Tensor) else \
+                torch.tensor([operator.index(x) for x in m], dtype=torch.int64)
+        except (TypeError, ValueError, RuntimeError, OverflowError) as e:
+            raise TypeError(f"recommend: where's {name} mask must be an int or integers ({e})") from None
+        if t.numel() != Q:
+            raise ValueError(f"recommend: where's {name} mask has {t.numel()} entries for {Q} queries")
+    if t.numel() and (int(t.min()) < -(1 << 31) or int(t.max()) >= 1 << 32):
+        raise ValueError(f"recommend: where's {name} mask has a value outside 32 bits")
+    return torch.where(t >= 1 << 31, t - (1 << 32), t)
+
+
+def _where_arg(attrs, where, M: int, Q: int):
+    """topk_rows' filter arguments, checked: None without a filter, else the int32 [Q, 3] table of
+    (any, all, none) rows, on the device of whichever mask was a device tensor (the CPU otherwise)."""
+    if attrs is None and where is None:
+        return None
+    if attrs is None:
+        raise ValueError("recommend: where needs attrs (the candidates' attribute words)")
+    if where is None:
+        raise ValueError("recommend: attrs needs where=(any, all, none)")
+    if not isinstance(attrs, torch.Tensor) or attrs.dtype != torch.int32 or attrs.dim() != 1:
+        raise TypeError("recommend: attrs must be an int32 tensor [M]")
+    if attrs.numel() != M:
+        raise ValueError(f"recommend: attrs has {attrs.numel()} entries for {M} candidates")
+    if isinstance(where, (str, bytes, torch.Tensor)) or not hasattr(where, "__len__") or len(where) != 3:
+        raise ValueError("recommend: where is (any, all, none)")
+    cols = [_mask_column(n, m, Q) for n, m in zip(("any", "all", "none"), where)]
+    dev = next((c.device for c in cols if c.is_cuda), torch.device("cpu"))
+    return torch.stack([c.to(dev).expand(Q) for c in cols], 1).to(torch.int32)
+
+
 def topk_rows(queries: torch.Tensor, picked: torch.Tensor, candidates: torch.Tensor, k: int, excl=None,
-              cap: int | None = None, subset: int | None = None, index_dtype: torch.dtype = torch.int64):
+              cap: int | None = None, subset: int | None = None, index_dtype: torch.dtype = torch.int64,
+              attrs: torch.Tensor | None = None, where=None):
     """(idx [Q, k] of ``index_dtype``, int64 by default; score f32 [Q, k]) on the device: for query
     row queries[picked[q]], the k best rows of ``candidates`` by cosine score that its exclusion row
     does not name, in rank order (score descending, candidate index ascending; NaN first).
@@ -100,7 +177,17 @@ def topk_rows(queries: torch.Tensor, picked: torch.Tensor, candidates: torch.Ten
     Queries are processed in blocks of at most BLOCK_BYTES of list workspace.
     index_dtype: torch.int64 (the default, what indexing wants) or torch.int32, the kernel's own
     index buffer handed on unconverted (what lgcn_amd.metrics.rank_metrics reads): a view of the
-    first Q rows of this call's padded buffer, which lives as long as the view does."""
+    first Q rows of this call's padded buffer, which lives as long as the view does.
+    attrs / where: an attribute filter, tested on the device where the score is tested (both or
+    neither). attrs is int32 [M] on the device, one 32-bit attribute word per candidate (attr_bits
+    makes them from labels); where is (any, all, none), each member an int — [0, 2**32) is taken as
+    the bit pattern, bit 31 being the int32's sign — or an integer tensor / sequence with one mask
+    per query, None for 0. Candidate j passes for query q when attrs[j] & none == 0,
+    attrs[j] & all == all and (any == 0 or attrs[j] & any != 0); only candidates that pass and are
+    not excluded are ranked. Under a filter a query short of k eligible candidates is padded with
+    -1 / -inf above ``cap`` too, as long as the candidates that pass for it fit ``cap`` (RuntimeError
+    otherwise); the ValueError above is left for M minus the excluded falling below k. topk_items,
+    topk_users, topk_rows_diverse and metrics.evaluate_ranking hand both on."""
     k = int(k)
     if index_dtype not in (torch.int64, torch.int32):
         raise ValueError(f"recommend: index_dtype must be torch.int64 or torch.int32, got {index_dtype}")
@@ -114,8 +201,11 @@ def topk_rows(queries: torch.Tensor, picked: torch.Tensor, candidates: torch.Ten
     subset = max(SUBSET_MIN, SUBSET_PER_K * k) if subset is None else int(subset)
     if subset < 1:
         raise ValueError(f"recommend: subset={subset}")
+    masks = None
+    if attrs is not None or where is not None:
+        masks = _where_arg(attrs, where, candidates.shape[0], torch.as_tensor(picked).numel())
     lib = _ffi.load()
-    for t in (queries, candidates):
+    for t in (queries, candidates) if masks is None else (queries, candidates, attrs):
         _ffi.require_device(t, "recommend")
     dev = queries.device
     d, M = queries.shape[1], candidates.shape[0]
@@ -150,6 +240,10 @@ def topk_rows(queries: torch.Tensor, picked: torch.Tensor, candidates: torch.Ten
     thr = torch.empty(blk, dtype=torch.int32, device=dev)
     stride = max(1, -(-M // min(subset, cap)))
     S = -(-M // stride) if M else 0
+    if masks is not None:  # the kernels' [Qpad, 3] table (padding queries' rows are never read) and attribute words
+        wh = torch.zeros((Qpad, 3), dtype=torch.int32, device=dev)
+        wh[:Q] = masks.to(dev)
+        attrs = attrs.detach().contiguous()
 
     def ranked(q0, nb, qv, counts, dense_n, thr_out, emit):
         if ptr is None:
@@ -160,8 +254,13 @@ def topk_rows(queries: torch.Tensor, picked: torch.Tensor, candidates: torch.Ten
             ex = (ptr.data_ptr() + q0 * 8, eidx.data_ptr(), None, R - q0)
         outs = (out_idx.data_ptr() + q0 * k * 4, out_score.data_ptr() + q0 * k * 4,
                 out_n.data_ptr() + q0 * 4) if emit else (None, None, None)
-        _ffi.check(lib.lgcn_select_topk_ranked(lkey.data_ptr(), lidx.data_ptr(), counts, dense_n, cap, k, nb, qv, *ex,
-                                               thr_out, *outs, s), "lgcn_select_topk_ranked")
+        if masks is None:
+            _ffi.check(lib.lgcn_select_topk_ranked(lkey.data_ptr(), lidx.data_ptr(), counts, dense_n, cap, k, nb, qv,
+                                                   *ex, thr_out, *outs, s), "lgcn_select_topk_ranked")
+        else:
+            _ffi.check(lib.lgcn_select_topk_ranked_attr(lkey.data_ptr(), lidx.data_ptr(), counts, dense_n, cap, k, nb,
+                                                        qv, *ex, thr_out, *outs, attrs.data_ptr(),
+                                                        wh.data_ptr() + q0 * 12, s), "lgcn_select_topk_ranked_attr")
 
     for q0 in range(0, Qpad, blk):
         nb = min(blk, Qpad - q0)
@@ -189,8 +288,14 @@ def topk_rows(queries: torch.Tensor, picked: torch.Tensor, candidates: torch.Ten
         ranked(q0, nb, qv, None, S, thr.data_ptr(), False)
         for _ in range(8):
             lcnt.zero_()
-            _ffi.check(lib.lgcn_score_filter(qptr, nb, qv, Cn.data_ptr(), M, 1, D, thr.data_ptr(), lkey.data_ptr(),
-                                             lidx.data_ptr(), lcnt.data_ptr(), cap, s), "lgcn_score_filter")
+            if masks is None:
+                _ffi.check(lib.lgcn_score_filter(qptr, nb, qv, Cn.data_ptr(), M, 1, D, thr.data_ptr(), lkey.data_ptr(),
+                                                 lidx.data_ptr(), lcnt.data_ptr(), cap, s), "lgcn_score_filter")
+            else:  # only candidates that pass enter a list
+                _ffi.check(lib.lgcn_score_filter_attr(qptr, nb, qv, Cn.data_ptr(), M, 1, D, thr.data_ptr(),
+                                                      lkey.data_ptr(), lidx.data_ptr(), lcnt.data_ptr(), cap,
+                                                      attrs.data_ptr(), wh.data_ptr() + q0 * 12, s),
+                           "lgcn_score_filter_attr")
             longest, few = torch.stack([lcnt[:qv].max().to(torch.int64), fewest]).tolist()  # the block's host read
             if few < k:
                 raise ValueError(f"recommend: a query has {few} eligible candidates, fewer than k={k} "
@@ -202,7 +307,9 @@ def topk_rows(queries: torch.Tensor, picked: torch.Tensor, candidates: torch.Ten
             # among them is a valid, tighter threshold; filter again
             ranked(q0, nb, qv, lcnt.data_ptr(), 0, thr.data_ptr(), False)
         else:
-            raise RuntimeError("recommend: candidate lists kept overflowing (scores too concentrated for the capacity)")
+            raise RuntimeError("recommend: candidate lists kept overflowing (scores too concentrated for the capacity"
+                               + ("" if masks is None else f", or more than cap={cap} candidates pass the filter of a query "
+                                                           f"that cannot fill k={k}") + ")")
     return (out_idx[:Q].to(torch.int64) if index_dtype == torch.int64 else out_idx[:Q]), out_score[:Q].clone()
 
 
@@ -284,8 +391,8 @@ def topk_rows_diverse(queries: torch.Tensor, picked: torch.Tensor, candidates: t
 
     pool: default max(4 * k, 64); whatever is asked for is clamped to what exists and what the
     re-rank kernel holds, min(M, MMR_MAX_POOL, MMR_MAX_LDS_BYTES // (4 * D)) with D the padded
-    width, and a pool that ends up below k is a ValueError. excl and kw (cap, subset, index_dtype)
-    are topk_rows'."""
+    width, and a pool that ends up below k is a ValueError. excl and kw (cap, subset, index_dtype,
+    attrs, where) are topk_rows'; under a filter a query's pool holds passing candidates only."""
     k, diversity = int(k), _diversity(diversity)
     if k < 1:
         raise ValueError(f"recommend: k={k} outside [1, {MMR_MAX_POOL}]")
@@ -332,12 +439,14 @@ def intra_list_diversity(pair: torch.Tensor, n: torch.Tensor, ks) -> torch.Tenso
 
 def topk_items(user_emb: torch.Tensor, item_emb: torch.Tensor, users, k: int, seen=None, **kw):
     """The k best items for each user index in ``users``; seen: seen_csr(..., by="user") over all
-    users (row u is user u's), whose items are left out. Returns topk_rows' (idx, score)."""
+    users (row u is user u's), whose items are left out. Returns topk_rows' (idx, score). kw: topk_rows'
+    cap, subset, index_dtype, attrs and where (the items' attribute words; one filter per user or one for all)."""
     users = torch.as_tensor(users).view(-1)
     return topk_rows(user_emb, users, item_emb, k, excl=None if seen is None else (seen[0], seen[1], users), **kw)
 
 
 def topk_users(user_emb: torch.Tensor, item_emb: torch.Tensor, items, k: int, seen=None, **kw):
-    """The k best users for each item index in ``items``; seen: seen_csr(..., by="item")."""
+    """The k best users for each item index in ``items``; seen: seen_csr(..., by="item"); kw as
+    topk_items' (attrs are then the users' attribute words)."""
     items = torch.as_tensor(items).view(-1)
     return topk_rows(item_emb, items, user_emb, k, excl=None if seen is None else (seen[0], seen[1], items), **kw)

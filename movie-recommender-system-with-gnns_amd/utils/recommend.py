@@ -15,6 +15,10 @@ were not in the training graph from the movies they name (fold-in, lgcn_amd.fold
 ``python utils/recommend.py --movies 1,296,318``). ``rank_for_user`` answers the counterpart of a
 list: where do these movies rank for this user, among all the user could be served (exact positions,
 lgcn_amd.metrics.rank_positions on the device; ``python utils/recommend.py USER_ID --rank 1,296,318``).
+``genres=`` / ``genres_all=`` / ``without_genres=`` (recommend_for_users, recommend_for_histories) serve
+"ten comedies", "anything but horror": the ``genres`` column of movies.csv as one attribute word per
+movie (``genre_table``), tested on the device where the score is tested
+(``python utils/recommend.py USER_ID --genres Comedy,Romance --without Horror``, likewise with ``--movies``).
 Not carried over: the plotting (``visualizations``) and the import-time seeding (nothing here draws
 random numbers). Unknown ids are answered without touching the GPU; everything else needs the model
 on a ROCm device (lgcn_amd._ffi.LgcnError otherwise, there is no CPU fallback).
@@ -59,6 +63,49 @@ def _id_map(handler, name: str, forward: Dict[int, int]) -> Dict[int, int]:
 def _title_of(movies) -> Dict[int, str]:
     first = movies.drop_duplicates("movieId")
     return dict(zip(first["movieId"].tolist(), first["title"].tolist()))
+
+
+NO_GENRES = '(no genres listed)'  # movies.csv's placeholder: no bit
+
+
+def genre_table(handler: Any):
+    """(vocabulary, attrs) of the handler's movies: the sorted distinct labels of
+    ``handler.movies['genres']`` split on '|' — '(no genres listed)', empty and missing values give no
+    label — and the int32 [num_items] attribute words in item-index order (CPU), bit b set for
+    vocabulary[b] (lgcn_amd.recommend.attr_bits). A movie of ``movie_id_map`` without a row in
+    ``movies`` gets 0."""
+    movies = handler.movies.drop_duplicates("movieId")
+    if "genres" not in movies.columns:
+        raise ValueError("genre_table: the handler's movies have no 'genres' column")
+    labels_of = {}
+    for movie_id, g in zip(movies["movieId"].tolist(), movies["genres"].tolist()):
+        parts = g.split('|') if isinstance(g, str) else []
+        labels_of[movie_id] = [x.strip() for x in parts if x.strip() and x.strip() != NO_GENRES]
+    vocabulary = sorted({x for labels in labels_of.values() for x in labels})
+    num_users = len(handler.user_id_map)
+    rows: list = [[] for _ in handler.movie_id_map]
+    for movie_id, index in handler.movie_id_map.items():
+        rows[index - num_users] = labels_of.get(movie_id, [])
+    return vocabulary, _rec.attr_bits(rows, vocabulary)
+
+
+def _genre_filter(who: str, handler: Any, genres, genres_all, without_genres):
+    """topk_rows' attrs / where keywords of one genre filter for the whole call (attrs still on the
+    CPU); {} when all three are None. An unknown name is a ValueError that lists the vocabulary."""
+    if genres is None and genres_all is None and without_genres is None:
+        return {}
+    vocabulary, attrs = genre_table(handler)
+    masks = []
+    for names in (genres, genres_all, without_genres):
+        if isinstance(names, str):
+            names = [names]
+        mask = 0
+        for name in names or ():
+            if name not in vocabulary:
+                raise ValueError(f"{who}: unknown genre {name!r}; the handler's movies have {vocabulary}")
+            mask |= 1 << vocabulary.index(name)
+        masks.append(mask)
+    return {"attrs": attrs, "where": tuple(masks)}
 
 
 def _ranked(idx: torch.Tensor, score: torch.Tensor):
@@ -114,7 +161,8 @@ def recommend_from_movie(model: torch.nn.Module, movie_id: int, data_handler: An
 def recommend_for_users(model: torch.nn.Module, user_ids: Sequence[int], data_handler: Any, k: int = 10,
                         exclude_seen: bool = True, train_edge_index: Optional[torch.Tensor] = None,
                         diversity: Optional[float] = None, pool: Optional[int] = None,
-                        explain: Optional[int] = None
+                        explain: Optional[int] = None, genres: Optional[Sequence[str]] = None,
+                        genres_all: Optional[Sequence[str]] = None, without_genres: Optional[Sequence[str]] = None
                         ) -> List[Union[Dict[str, str], List[Dict[str, Any]]]]:
     """One entry per id of ``user_ids``: the user's k best movies as [{'movie_id', 'title', 'score'}],
     or {'error': 'Invalid user ID'} for an unknown id. With ``exclude_seen`` the movies a user has an
@@ -129,9 +177,16 @@ def recommend_for_users(model: torch.nn.Module, user_ids: Sequence[int], data_ha
     an edge to — in the same edge set ``exclude_seen`` uses, whether or not it is set — whose rows have
     the largest cosine to the recommended movie's row, best first (lgcn_amd.explain.explain_items on
     the rows the list was ranked with); fewer than r for a shorter history. It explains the re-ranked
-    list when ``diversity`` is set."""
+    list when ``diversity`` is set.
+    ``genres`` / ``genres_all`` / ``without_genres`` (sequences of genre names; None for all three:
+    today's calls) keep only movies with at least one genre of ``genres``, every genre of
+    ``genres_all`` and none of ``without_genres`` — one filter for the whole call, genre_table's
+    attribute words tested on the device (topk_rows' attrs / where). A list is shorter than k when
+    fewer movies are left; an unknown name is a ValueError that lists the vocabulary. They combine
+    with ``diversity`` (the pool holds passing movies only) and ``explain``."""
     if diversity is None and pool is not None:
         raise ValueError("recommend_for_users: pool is the re-rank's pool and needs diversity")
+    flt = _genre_filter("recommend_for_users", data_handler, genres, genres_all, without_genres)
     if explain is not None:
         explain = int(explain)
         if explain < 1 or explain > _explain.MAX_R:
@@ -143,6 +198,8 @@ def recommend_for_users(model: torch.nn.Module, user_ids: Sequence[int], data_ha
     if not known:
         return out
     dev = model.user_embedding.weight.device
+    if flt:
+        flt["attrs"] = flt["attrs"].to(dev)
     users = torch.tensor([u for _, u in known], dtype=torch.int64, device=dev)
     excl = history = None
     if exclude_seen or explain is not None:
@@ -153,10 +210,10 @@ def recommend_for_users(model: torch.nn.Module, user_ids: Sequence[int], data_ha
     with torch.no_grad():
         user_emb, item_emb = model.get_embeddings(user_indices=users, item_indices=torch.arange(num_items, device=dev))
         if diversity is None:
-            idx, score = _rec.topk_rows(user_emb, torch.arange(users.numel()), item_emb, k, excl=excl)
+            idx, score = _rec.topk_rows(user_emb, torch.arange(users.numel()), item_emb, k, excl=excl, **flt)
         else:
             idx, score = _rec.topk_rows_diverse(user_emb, torch.arange(users.numel()), item_emb, k, diversity,
-                                                pool=pool, excl=excl)[:2]
+                                                pool=pool, excl=excl, **flt)[:2]
         why = None if explain is None else _explain.explain_items(item_emb, users, idx, history, r=explain)
     id_movie = _id_map(data_handler, "id_movie_map", movie_id_map)
     title_of = _title_of(data_handler.movies)
@@ -179,7 +236,9 @@ def recommend_for_histories(model: torch.nn.Module, histories: Sequence[Sequence
                             exclude_history: bool = True, train_edge_index: Optional[torch.Tensor] = None,
                             embeddings: str = "raw", weights: Optional[Sequence[Sequence[float]]] = None,
                             diversity: Optional[float] = None, pool: Optional[int] = None,
-                            explain: Optional[int] = None
+                            explain: Optional[int] = None, genres: Optional[Sequence[str]] = None,
+                            genres_all: Optional[Sequence[str]] = None,
+                            without_genres: Optional[Sequence[str]] = None
                             ) -> List[Union[Dict[str, str], List[Dict[str, Any]]]]:
     """Lists for people the model never saw — someone who has just rated a few films, an anonymous
     session: one entry per history of ``histories`` (each a sequence of MovieLens movie ids), the k
@@ -195,8 +254,8 @@ def recommend_for_histories(model: torch.nn.Module, histories: Sequence[Sequence
     "propagated" folds against lgcn_amd.foldin.layer_tables' S_item and ranks
     model(train_edge_index)'s item rows, which gives the new user the row the K-layer model would.
     ``exclude_history`` leaves the history's movies out of the list. ``diversity`` / ``pool`` /
-    ``explain`` are recommend_for_users'; the 'because' movies come from the supplied history
-    (lgcn_amd.explain.explain_rows). All histories are served by one fold-in and one ranking call;
+    ``explain`` and ``genres`` / ``genres_all`` / ``without_genres`` are recommend_for_users'; the
+    'because' movies come from the supplied history (lgcn_amd.explain.explain_rows). All histories are served by one fold-in and one ranking call;
     if no history has a known id the answer comes without touching the model or the GPU."""
     if embeddings not in ("raw", "propagated"):
         raise ValueError(f"recommend_for_histories: embeddings must be 'raw' or 'propagated', got {embeddings!r}")
@@ -208,6 +267,7 @@ def recommend_for_histories(model: torch.nn.Module, histories: Sequence[Sequence
             raise ValueError(f"recommend_for_histories: explain={explain} outside [1, {_explain.MAX_R}]")
     if weights is not None and len(weights) != len(histories):
         raise ValueError(f"recommend_for_histories: {len(weights)} weight lists for {len(histories)} histories")
+    flt = _genre_filter("recommend_for_histories", data_handler, genres, genres_all, without_genres)
     user_id_map, movie_id_map = data_handler.user_id_map, data_handler.movie_id_map
     num_users, num_items = len(user_id_map), len(movie_id_map)
     out: list = [{'error': 'No known movie IDs'} for _ in histories]
@@ -227,6 +287,8 @@ def recommend_for_histories(model: torch.nn.Module, histories: Sequence[Sequence
     if not slots:
         return out
     dev = model.user_embedding.weight.device
+    if flt:
+        flt["attrs"] = flt["attrs"].to(dev)
     ptr = torch.tensor([0] + [len(r) for r in rows], dtype=torch.int64).cumsum(0).to(dev)
     hidx = torch.tensor([i for r in rows for i in r], dtype=torch.int32, device=dev)
     hw = None if weights is None else torch.tensor([x for r in row_w for x in r], dtype=torch.float32, device=dev)
@@ -245,10 +307,10 @@ def recommend_for_histories(model: torch.nn.Module, histories: Sequence[Sequence
         queries = _foldin.fold_in(history, table, count=degree, weights=hw).rows
         excl = history if exclude_history else None
         if diversity is None:
-            idx, score = _rec.topk_rows(queries, torch.arange(len(slots)), item_emb, k, excl=excl)
+            idx, score = _rec.topk_rows(queries, torch.arange(len(slots)), item_emb, k, excl=excl, **flt)
         else:
             idx, score = _rec.topk_rows_diverse(queries, torch.arange(len(slots)), item_emb, k, diversity,
-                                                pool=pool, excl=excl)[:2]
+                                                pool=pool, excl=excl, **flt)[:2]
         why = None if explain is None else _explain.explain_rows(idx, history, item_emb, r=explain)
     id_movie = _id_map(data_handler, "id_movie_map", movie_id_map)
     title_of = _title_of(data_handler.movies)
@@ -312,6 +374,17 @@ if __name__ == '__main__':
     from data.dataset_handler import MovieLensDataHandler
     from models.light_gcn import LightGCN
 
+    def option(flag):  # --flag A,B taken out of the argument list: the names, or None
+        if flag not in sys.argv[1:-1]:
+            return None
+        at = sys.argv.index(flag)
+        names = [x.strip() for x in sys.argv[at + 1].split(',') if x.strip()]
+        del sys.argv[at:at + 2]
+        return names
+
+    # a genre filter: --genres Comedy,Romance (any of) --genres-all Comedy,Romance (each of) --without Horror
+    genre_kw = dict(genres=option('--genres'), genres_all=option('--genres-all'), without_genres=option('--without'))
+    filtered = any(v is not None for v in genre_kw.values())
     handler = MovieLensDataHandler('data/movielens-25m/ratings.csv', 'data/movielens-25m/movies.csv')
     model = LightGCN(*handler.get_num_users_items()).to('cuda')
     if os.path.exists('best_model.pth'):
@@ -319,7 +392,7 @@ if __name__ == '__main__':
     model.eval()
     if len(sys.argv) > 2 and sys.argv[1] == '--movies':  # someone the model never saw: --movies 1,296,318
         watched = [int(m) for m in sys.argv[2].split(',') if m.strip()]
-        served = recommend_for_histories(model, [watched], handler, k=TOP_N, explain=3)[0]
+        served = recommend_for_histories(model, [watched], handler, k=TOP_N, explain=3, **genre_kw)[0]
         if isinstance(served, dict):
             sys.exit(served['error'])
         print(f"Top 10 Recommendations for someone who watched {', '.join(map(str, watched))}:")
@@ -342,8 +415,9 @@ if __name__ == '__main__':
             print(f"{r['movie_id']}: {r['title'] or '?'}: {where}")
         sys.exit(0)
     seen_items = ei[1, ei[0] == handler.user_id_map[uid]] - handler.num_users
-    result = recommend_from_user(model, uid, handler, seen_items)
-    why = recommend_for_users(model, [uid], handler, k=TOP_N, train_edge_index=ei, explain=3)[0]
+    why = recommend_for_users(model, [uid], handler, k=TOP_N, train_edge_index=ei, explain=3, **genre_kw)[0]
+    # the reference's own call serves the unfiltered list; a genre filter is recommend_for_users' alone
+    result = {'recommendations': why} if filtered else recommend_from_user(model, uid, handler, seen_items)
     because = {rec['title']: rec['because'] for rec in why}
     print(f"Top 10 Recommendations for user {uid}:")
     for rank, rec in enumerate(result['recommendations'], 1):

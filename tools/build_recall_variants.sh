@@ -2,7 +2,7 @@
 # Builds k_score_filter A/B variants of liblgcn.so into tools/_variants/ (see tools/recall_variants.py).
 # The variants are not in the product source: each is spliced into a copy of the sources here
 # (NO_MFMA: the MFMA chain of lgcn_scoretile.h's ScoreTile::scores replaced by one multiply per
-# accumulator; NO_EPI: k_score_filter's epilogue in lgcn_recall.hip skipped).
+# accumulator; NO_EPI: k_score_filter's epilogue in lgcn_recall_lists.h skipped).
 set -e
 R=$(cd "$(dirname "$0")/.." && pwd)
 C=$R/movie-recommender-system-with-gnns_amd/csrc
@@ -25,7 +25,7 @@ splice("lgcn_scoretile.h", "        constexpr int G = (H / 4) >= 4 ? 4 : (H / 4)
         if (false)
 #endif
 """, before=False)
-splice("lgcn_recall.hip",
+splice("lgcn_recall_lists.h",
        "        // epilogue: column = candidate j (this lane's), rows = queries; branch-free test, and\n",
        """#ifdef LGCN_VARIANT_NO_EPI
         if (acc[0] == 12345.f && acc[15] == 54321.f) list_n[0] = 1;  // keep acc live; never true
