@@ -643,9 +643,14 @@ int lgcn_select_topk_stl(uint32_t* list_key, int32_t* list_idx, int64_t cap, int
  *   padding queries [Qvalid, Qpad): thr_out = 0xFFFFFFFF, out_n = 0, every slot -1 / -inf.
  * Limits: 1 <= k <= LGCN_RANKED_MAX_K (the winners are ranked in LDS), k <= cap <=
  * LGCN_RANKED_MAX_CAP (one eligibility bit per list entry in LDS; LGCN_E_UNSUPPORTED above it).
- * Both modes may be asked for in one call. */
+ * Both modes may be asked for in one call.
+ * Lists that name a candidate more than once (lgcn_score_lists' may; the filter's never do): with
+ * list_n set dense_n is not read, except that dense_n == LGCN_RANKED_REPEATS says so. Equal entries
+ * then take adjacent slots (an entry named twice is ranked twice); without it the result for such a
+ * list is unspecified. For lists without repeats both give the same output. */
 #define LGCN_RANKED_MAX_K 1024
 #define LGCN_RANKED_MAX_CAP 262144
+#define LGCN_RANKED_REPEATS (-1)
 int lgcn_select_topk_ranked(const uint32_t* list_key, const int32_t* list_idx, const int32_t* list_n, int32_t dense_n,
                             int32_t cap, int32_t k, int64_t Qpad, int64_t Qvalid, const int64_t* excl_ptr,
                             const int32_t* excl_idx, const int64_t* excl_row, int64_t excl_rows, uint32_t* thr_out,
@@ -901,6 +906,34 @@ int lgcn_rank_positions(const float* Qn, int64_t Qpad, int64_t Q, const float* C
                         const int64_t* seen_row, int64_t seen_rows, const int64_t* out_ptr, int64_t nnz,
                         int32_t* pos_out, uint32_t* key_out, int32_t* eligible_out, void* workspace,
                         size_t workspace_bytes, int32_t stages, lgcn_stream_t stream);
+
+/* Per-query candidate sets (added under ABI 11, purely additive): query q ranks the entries of its
+ * own row of a CSR and nothing else — a watchlist, a retrieval stage's output, one held-out item
+ * among sampled negatives. lgcn_score_lists scores each row into the (key, index) lists
+ * lgcn_select_topk_ranked / lgcn_select_topk_ranked_attr read (list mode: list_n set), at the cost of
+ * the rows' lengths: no [Q, M] work, no padded gather, no workspace (csrc/lgcn_recall_among.hip).
+ *   Qn [Qvalid, D], Cn [M, D]: unit rows as lgcn_normalize_rows writes them, both 16-byte aligned, D
+ *     one of lgcn_recall_width's widths.
+ *   among: CSR (among_ptr int64[among_rows + 1], among_idx int32) with the row conventions of the
+ *     exclusion CSR above: query q uses row among_row[q] (row q when among_row is NULL); a row
+ *     outside [0, among_rows) is empty. Entries may come in any order and need not be distinct (an
+ *     entry named twice is listed twice). An entry outside [0, M) names nothing and takes no slot.
+ *   For the p-th kept entry j of query q (the order within a list is unspecified; the ranked
+ *   selection imposes its own):
+ *       list_idx[q * cap + p] = j,
+ *       list_key[q * cap + p] = exactly the uint32 key lgcn_score_filter gives the pair (q, j), bit
+ *                               for bit (the same v_mfma_f32_32x32x2_f32 chain; NaN is 0xFFFFFFFF).
+ *   list_n[q] = the number of kept entries, written here (the caller does not zero it); entries
+ *     past cap are counted but not stored, as the filter has it.
+ * No floating-point atomics; the outputs are bitwise reproducible up to the order within a list.
+ * LGCN_E_ARG: a null pointer (among_row may be NULL), cap < 1, D not one of lgcn_recall_width's
+ * widths, Qvalid, M or among_rows below 0, Qvalid or M above INT32_MAX, a misaligned Qn or Cn.
+ * Checked before any HIP call; Qvalid == 0 returns LGCN_OK without a launch. Allocates nothing,
+ * reads nothing back, does not synchronise. */
+int lgcn_score_lists(const float* Qn, int64_t Qvalid, const float* Cn, int64_t M, int32_t D,
+                     const int64_t* among_ptr, const int32_t* among_idx, const int64_t* among_row,
+                     int64_t among_rows, uint32_t* list_key, int32_t* list_idx, int32_t* list_n, int32_t cap,
+                     lgcn_stream_t stream);
 
 /* Host-only (no GPU): `draws` consecutive numpy legacy np.random.choice(n, size, replace=False)
  * calls (reference utils/train_test.py:187) on the MT19937 state (key[624], *pos) of

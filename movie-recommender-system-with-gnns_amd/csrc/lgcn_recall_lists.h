@@ -199,10 +199,19 @@ constexpr int kSelBlock = 1024;
 // entries t, t + 1024, ...).
 // kAttr (lgcn_select_topk_ranked_attr): step 1 also requires attr_passes of the entry's candidate
 // against the query's masks (uniform over the workgroup); everything after it reads the bit.
+// kRepeats (dense_n == LGCN_RANKED_REPEATS beside list_n): a list may name a candidate more than once,
+// as lgcn_score_lists' may, so composites may be EQUAL, which step 3 above cannot take: copies of the
+// k-th composite T that straddle slot k make the gather `c >= T` take more than k entries, and the
+// guard `slot < k` may then drop a better entry instead of a copy; and equal winners compute the same
+// rank, so one slot is written twice and one never. This instantiation gathers only the entries
+// ABOVE T (at most k, by the definition of T) and counts the entries equal to T — they are all T —
+// which fill the slots that are left; equal winners above T take consecutive ranks in gather order.
+// A template parameter and not a change of step 3, so that the lists without repeats (every caller
+// before lgcn_score_lists) are ranked by the instruction stream they were ranked by.
 constexpr int kRankMaxK = LGCN_RANKED_MAX_K;
 constexpr int kRankMaxCap = LGCN_RANKED_MAX_CAP;
 
-template <bool kAttr>
+template <bool kAttr, bool kRepeats = false>
 __global__ __launch_bounds__(kSelBlock) void k_select_ranked(
     const uint32_t* __restrict__ list_key, const int32_t* __restrict__ list_idx, const int32_t* __restrict__ list_n,
     int32_t dense_n, int32_t cap, int32_t k, int64_t Qvalid, const int64_t* __restrict__ excl_ptr,
@@ -214,6 +223,7 @@ __global__ __launch_bounds__(kSelBlock) void k_select_ranked(
     __shared__ uint32_t hist[256];
     __shared__ unsigned long long s_prefix, s_mask;
     __shared__ uint32_t s_k, s_bin, s_cnt;
+    __shared__ uint32_t s_eq;  // kRepeats: entries equal to the k-th composite
     __shared__ int32_t red[kSelBlock / 64];
     const int64_t q = blockIdx.x;
     const int tid = threadIdx.x;
@@ -269,6 +279,7 @@ __global__ __launch_bounds__(kSelBlock) void k_select_ranked(
         s_k = static_cast<uint32_t>(k);
         s_bin = 0u;
         s_cnt = 0u;
+        if constexpr (kRepeats) s_eq = 0u;
     }
     __syncthreads();
     int32_t n_elig = 0;
@@ -330,6 +341,37 @@ __global__ __launch_bounds__(kSelBlock) void k_select_ranked(
     }
     if (thr_out && tid == 0) thr_out[q] = n_elig >= k ? static_cast<uint32_t>(T >> 32) : 0u;
     if (!out_idx) return;
+    if constexpr (kRepeats) {  // 3. with equal composites: see the head of the kernel
+        for (int32_t e = tid; e < n; e += kSelBlock) {
+            const unsigned long long c = composite(e);
+            if (c > T) {
+                const uint32_t slot = atomicAdd(&s_cnt, 1u);
+                if (slot < static_cast<uint32_t>(k)) win[slot] = c;
+            } else if (c != 0ull && c == T) {
+                atomicAdd(&s_eq, 1u);
+            }
+        }
+        __syncthreads();
+        const int32_t G = s_cnt < static_cast<uint32_t>(k) ? static_cast<int32_t>(s_cnt) : k;  // above T
+        const int32_t W = s_eq < static_cast<uint32_t>(k - G) ? G + static_cast<int32_t>(s_eq) : k;
+        for (int t = tid; t < k; t += kSelBlock) {
+            if (t < W) {
+                const unsigned long long c = t < G ? win[t] : T;
+                int32_t rank = t;  // the copies of T stand below everything gathered, in their slots
+                if (t < G) {
+                    rank = 0;
+                    for (int32_t j = 0; j < G; ++j) rank += (win[j] > c) | ((win[j] == c) & (j < t));
+                }
+                out_idx[q * k + rank] = static_cast<int32_t>(0xFFFFFFFFu - static_cast<uint32_t>(c));
+                out_score[q * k + rank] = key_score(static_cast<uint32_t>(c >> 32));
+            } else {
+                out_idx[q * k + t] = -1;
+                out_score[q * k + t] = ninf;
+            }
+        }
+        if (tid == 0) out_n[q] = W;
+        return;
+    }
     // 3. gather the winners, rank them, store in rank order
     for (int32_t e = tid; e < n; e += kSelBlock) {
         const unsigned long long c = composite(e);
@@ -401,6 +443,12 @@ int select_ranked(const char* me, const uint32_t* list_key, const int32_t* list_
     if (emit && !out_n) return fail(LGCN_E_ARG, "%s: out_n is null", me);
     AttrArgs<kAttr> fa;
     if constexpr (kAttr) fa = {attr, where};
+    if (list_n && dense_n == LGCN_RANKED_REPEATS) {  // lists that may name a candidate more than once
+        k_select_ranked<kAttr, true><<<dim3(static_cast<unsigned>(Qpad)), kSelBlock, 0, as_stream(stream)>>>(
+            list_key, list_idx, list_n, dense_n, cap, k, Qvalid, excl_ptr, excl_idx, excl_row, excl_rows, thr_out,
+            out_idx, out_score, out_n, fa);
+        return check_launch(kAttr ? "k_select_ranked<attr, repeats>" : "k_select_ranked<repeats>");
+    }
     k_select_ranked<kAttr><<<dim3(static_cast<unsigned>(Qpad)), kSelBlock, 0, as_stream(stream)>>>(
         list_key, list_idx, list_n, dense_n, cap, k, Qvalid, excl_ptr, excl_idx, excl_row, excl_rows, thr_out, out_idx,
         out_score, out_n, fa);

@@ -144,6 +144,33 @@ struct ScoreTile {
         }
         return score_key(acc[0]);  // row 4h of the tile, column i: every row is the query
     }
+
+    // Lane (i, h)'s half of row `row` of a table of D-wide rows, as row_keys reads it from memory:
+    // float4 v holds columns h*D/2 + 4v .. 4v + 3. row < 0: none, zeros (nothing is read).
+    static __device__ __forceinline__ void load_half(const float* __restrict__ rows, int64_t row, int h,
+                                                     float4 (&v)[H / 4]) {
+        const float4* src = reinterpret_cast<const float4*>(rows + (row < 0 ? 0 : row) * D + h * H);
+#pragma unroll
+        for (int x = 0; x < H / 4; ++x) v[x] = row >= 0 ? src[x] : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+
+    // row_keys on operands already in registers (load_half's): qa the query's half, b the half of
+    // candidate i's row. The same tile, the same steps in the same order, so the same key; a caller
+    // keeps qa for a whole row of candidates and has the next b in flight while this chain runs
+    // (lgcn_recall_among.hip).
+    static __device__ __forceinline__ uint32_t row_keys(const float4 (&qa)[H / 4], const float4 (&b)[H / 4]) {
+        f32x16 acc;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+#pragma unroll
+        for (int v = 0; v < H / 4; ++v) {
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(qa[v].x, b[v].x, acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(qa[v].y, b[v].y, acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(qa[v].z, b[v].z, acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(qa[v].w, b[v].w, acc, 0, 0, 0);
+        }
+        return score_key(acc[0]);
+    }
 };
 
 // The launch of a tile kernel over nqg >= 1 query groups and M > 0 candidates: candidate chunks are a

@@ -29,6 +29,7 @@ ABI_VERSION = 11  # LGCN_ABI_VERSION of include/lgcn.h this binding speaks
 DIGEST_BLOCKS = 1024  # LGCN_DIGEST_BLOCKS
 RANKED_MAX_K = 1024  # LGCN_RANKED_MAX_K
 RANKED_MAX_CAP = 262144  # LGCN_RANKED_MAX_CAP
+RANKED_REPEATS = -1  # LGCN_RANKED_REPEATS: dense_n beside list_n for lists that may name a candidate twice
 METRICS_MAX_CUTOFFS = 8  # LGCN_METRICS_MAX_CUTOFFS
 MMR_MAX_POOL = 512  # LGCN_MMR_MAX_POOL
 MMR_MAX_LDS_BYTES = 131072  # LGCN_MMR_MAX_LDS_BYTES
@@ -158,6 +159,7 @@ _SIGS = {
     "lgcn_rank_positions_workspace_size": ([_i64, _i64, ctypes.POINTER(_sz)], ctypes.c_int),
     "lgcn_rank_positions": ([_vp, _i64, _i64, _vp, _i64, _i32, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _i64,
                              _vp, _vp, _vp, _vp, _sz, _i32, _vp], ctypes.c_int),
+    "lgcn_score_lists": ([_vp, _i64, _vp, _i64, _i32, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i32, _vp], ctypes.c_int),
     "lgcn_legacy_choice": ([_vp, _vp, _i64, _i64, _i64, _vp], ctypes.c_int),
     "lgcn_slice_schedule_workspace_size": ([_i64, _i64, _i32, _i32, _vp, _vp], ctypes.c_int),
     "lgcn_slice_schedule_build": ([_vp, _vp, _i64, _i64, _vp, _i32, _i32, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp,
@@ -248,7 +250,7 @@ def load(path: os.PathLike | str | None = None) -> ctypes.CDLL:
 CSRC = _HERE.parent / "csrc"
 INCLUDE = _HERE.parent.parent / "include"
 # the translation units of liblgcn.so (lgcn_build.cpp carries the hash and is not hashed)
-SOURCES = ("lgcn_plan.hip", "lgcn_spmm.hip", "lgcn_optim.hip", "lgcn_bpr.hip", "lgcn_recall.hip", "lgcn_recall_attr.hip", "lgcn_metrics.hip", "lgcn_rerank.hip",
+SOURCES = ("lgcn_plan.hip", "lgcn_spmm.hip", "lgcn_optim.hip", "lgcn_bpr.hip", "lgcn_recall.hip", "lgcn_recall_attr.hip", "lgcn_recall_among.hip", "lgcn_metrics.hip", "lgcn_rerank.hip",
            "lgcn_explain.hip", "lgcn_foldin.hip", "lgcn_negatives.hip", "lgcn_rankpos.hip", "lgcn_rowadam.hip", "lgcn_exchange.hip", "lgcn_partition.cpp", "lgcn_sample.cpp", "lgcn_tuning.cpp", "lgcn_program.cpp")
 # the headers they include (csrc/), hashed and tracked as build dependencies with include/lgcn.h
 HEADERS = ("lgcn_common.h", "lgcn_exact.h", "lgcn_reg.h", "lgcn_ragged.h", "lgcn_scoretile.h", "lgcn_recall_lists.h")

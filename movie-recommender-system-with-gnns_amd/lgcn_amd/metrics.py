@@ -155,7 +155,11 @@ def evaluate_ranking(user_emb: torch.Tensor, item_emb: torch.Tensor, truth, ks=(
     builds it; seen: the training CSR whose items are left out of every user's ranking (None:
     nothing excluded); users: the user indices evaluated (default: every user with a non-empty
     truth row); ks: the cutoffs; topk_kw: recommend.topk_rows' cap / subset / attrs / where (an attribute
-    filter: the metrics of the filtered lists against the same truth).
+    filter: the metrics of the filtered lists against the same truth) and among (a candidate set per
+    user, seen's convention: a 2-tuple is a CSR over all users, a 3-tuple names each evaluated user's
+    row; the metrics of the lists ranked among the sets — the sampled-negative protocol's numbers
+    when a set is the user's held-out items and sampled negatives; a re-rank pool then holds set
+    entries only).
     One recommend.topk_items call for max(ks) items per user, one lgcn_rank_metrics launch, then
     summarize. Host reads: summarize's one; topk_rows' one per query block when the items exceed
     its dense capacity; and, when ``users`` is left to default, the size of torch.nonzero's result
@@ -178,6 +182,9 @@ def evaluate_ranking(user_emb: torch.Tensor, item_emb: torch.Tensor, truth, ks=(
     if users is None:
         users = torch.nonzero(ptr[1:] > ptr[:-1]).view(-1)
     users = torch.as_tensor(users).to(device=dev, dtype=torch.int64).view(-1)
+    among = topk_kw.get("among")
+    if among is not None and len(among) == 2:
+        topk_kw["among"] = (among[0], among[1], users)
     if diversity is not None:
         excl = None if seen is None else (seen[0], seen[1], users)
         lists = recommend.topk_rows_diverse(user_emb, users, item_emb, cs[-1], diversity, pool=pool, excl=excl,

@@ -17,6 +17,13 @@ any point and the host reads at most one value pair per query block.
     test a candidate's attribute word where they test its score: a list only ever holds candidates
     that pass, so a filter that passes 0.5 % of the items costs no capacity.
 
+    with among= (a candidate set per query, as a CSR: "rank these and only these" — a watchlist, a
+    retrieval stage's output, one held-out item among 99 sampled negatives) no filter runs at all:
+      queries longest row first, in blocks of capacity max(k, the block's longest row):
+                 lists = the row's keys  lgcn_score_lists (csrc/lgcn_recall_among.hip; cost: Σ row lengths)
+                 ranked emit             lgcn_select_topk_ranked[_attr]
+    and the list is the query's full ranking restricted to its row, bit for bit.
+
 Ranking rule: score descending, then candidate index ascending (NaN scores first). The threshold
 is formed from eligible subset entries only: it is then the k-th best of a subset of the eligible
 candidates, so it is a lower bound of the k-th best eligible score of all M, and the filtered list
@@ -86,6 +93,18 @@ def _excl_args(excl, dev, Q: int):
     if rows is not None:
         rows = rows.to(device=dev, dtype=torch.int64).contiguous()
     return ptr.to(dev).contiguous(), idx.to(dev).contiguous(), rows, ptr.numel() - 1
+
+
+def _row_lengths(ptr: torch.Tensor, rows, Q: int) -> torch.Tensor:
+    """int64 [Q] on ptr's device: the length of each query's row of the CSR ptr (rows[q], or q); 0 for
+    a row outside the CSR, as in the kernels (lgcn_ragged.h's ragged_row)."""
+    R = ptr.numel() - 1
+    r = torch.arange(Q, device=ptr.device) if rows is None else rows.to(torch.int64)
+    if R == 0:
+        return torch.zeros(Q, dtype=torch.int64, device=ptr.device)
+    inside = (r >= 0) & (r < R)
+    rc = r.clamp(0, R - 1)
+    return torch.where(inside, ptr[rc + 1] - ptr[rc], torch.zeros_like(rc)).clamp(min=0)
 
 
 def attr_bits(labels, vocabulary) -> torch.Tensor:
@@ -159,9 +178,137 @@ def _where_arg(attrs, where, M: int, Q: int):
     return torch.stack([c.to(dev).expand(Q) for c in cols], 1).to(torch.int32)
 
 
+def candidate_csr(lists, device=None):
+    """The ``among=`` CSR of per-query candidate lists: (ptr int64 [Q + 1], idx int32), row q holding
+    query q's candidate indices ascending and deduplicated. lists: a sequence of integer sequences
+    (or 1-D tensors), or an integer tensor [Q, N] whose negative entries are padding; negative
+    entries are dropped, an empty row stays an empty row. Plain torch ops, on ``device`` (default:
+    the tensor's own, the CPU for sequences)."""
+    if torch.is_tensor(lists):
+        if lists.dim() != 2 or lists.dtype.is_floating_point or lists.dtype.is_complex or lists.dtype == torch.bool:
+            raise TypeError("candidate_csr: a tensor of lists must be an integer tensor [Q, N]")
+        t = lists.detach().to(torch.int64)
+        if device is not None:
+            t = t.to(device)
+        Q = t.shape[0]
+        rows = torch.arange(Q, device=t.device).repeat_interleave(t.shape[1])
+        cols = t.reshape(-1)
+    else:
+        lists = [torch.as_tensor(r).reshape(-1) for r in lists]
+        for r in lists:
+            if r.numel() and (r.dtype.is_floating_point or r.dtype.is_complex or r.dtype == torch.bool):
+                raise TypeError(f"candidate_csr: candidate indices must be integers, got {r.dtype}")
+        dev = torch.device("cpu") if device is None else torch.device(device)
+        Q = len(lists)
+        lens = torch.tensor([r.numel() for r in lists], dtype=torch.int64)
+        rows = torch.arange(Q).repeat_interleave(lens).to(dev)
+        cols = torch.cat([r.to(device=dev, dtype=torch.int64) for r in lists] + [torch.zeros(0, dtype=torch.int64, device=dev)])
+    keep = cols >= 0
+    rows, cols = rows[keep], cols[keep]
+    if cols.numel() and int(cols.max()) > torch.iinfo(torch.int32).max:
+        raise ValueError("candidate_csr: a candidate index does not fit int32")
+    C = int(cols.max()) + 1 if cols.numel() else 1
+    key = torch.unique(rows * C + cols, sorted=True)
+    ptr = torch.zeros(Q + 1, dtype=torch.int64, device=cols.device)
+    if Q > 0:
+        ptr[1:] = torch.cumsum(torch.bincount(key // C, minlength=Q), 0)
+    return ptr, (key % C).to(torch.int32)
+
+
+def _among_blocks(lengths, k: int, block_bytes: int):
+    """[(a, b, capacity)] over queries sorted longest row first (lengths: the sorted row lengths, a
+    host sequence): a block's capacity is max(k, its longest row = its first) and it holds at most
+    block_bytes // (8 * capacity) queries, at least one."""
+    blocks, a, Q = [], 0, len(lengths)
+    while a < Q:
+        cap = max(k, int(lengths[a]))
+        b = min(Q, a + max(1, block_bytes // (8 * cap)))
+        blocks.append((a, b, cap))
+        a = b
+    return blocks
+
+
+def _topk_among(queries, picked, candidates, k: int, excl, index_dtype, attrs, where, among):
+    """topk_rows' among= path: see its docstring."""
+    Q = torch.as_tensor(picked).numel()
+    aptr, aidx, arow, _ = _serving.csr_arg("recommend", "among", among, Q)
+    masks = None
+    if attrs is not None or where is not None:
+        masks = _where_arg(attrs, where, candidates.shape[0], Q)
+    if excl is not None:
+        _serving.csr_arg("recommend", "excl", excl, Q)
+    # longest row first. The one host read of the call: the sorted row lengths, which give every
+    # block's boundaries and capacity at once (and the refusal of a row the selection cannot hold,
+    # before anything is loaded)
+    lens, order = torch.sort(_row_lengths(aptr, None if arow is None else arow.to(aptr.device), Q), descending=True,
+                             stable=True)
+    lengths = lens.cpu().numpy()
+    if Q and int(lengths[0]) > _ffi.RANKED_MAX_CAP:
+        raise ValueError(f"recommend: an among row has {int(lengths[0])} entries, above the ranked selection's "
+                         f"capacity {_ffi.RANKED_MAX_CAP}")
+    blocks = _among_blocks(lengths, k, BLOCK_BYTES)
+    lib = _ffi.load()
+    for t in (queries, candidates) if masks is None else (queries, candidates, attrs):
+        _ffi.require_device(t, "recommend")
+    dev = queries.device
+    d, M = queries.shape[1], candidates.shape[0]
+    if candidates.shape[1] != d:
+        raise ValueError("recommend: queries and candidates must have the same width")
+    D = _serving.width("recommend", d)
+    picked = torch.as_tensor(picked).to(device=dev, dtype=torch.int64).contiguous().view(-1)
+    if Q == 0:
+        return (torch.empty((0, k), dtype=index_dtype, device=dev),
+                torch.empty((0, k), dtype=torch.float32, device=dev))
+    eptr, eidx, erow, ER = _excl_args(excl, dev, Q)
+    aptr, aidx = aptr.to(dev).contiguous(), aidx.to(dev).contiguous()
+    if aidx.numel() == 0:  # every row is empty: the library still wants an address
+        aidx = torch.zeros(1, dtype=torch.int32, device=dev)
+    every = torch.arange(Q, device=dev)
+    arow = every if arow is None else arow.to(device=dev, dtype=torch.int64)
+    order = order.to(dev)
+    arow = arow[order].contiguous()
+    if eptr is not None:
+        erow = (every if erow is None else erow)[order].contiguous()
+    s = _ffi.stream_of(dev)
+    queries, candidates = queries.detach(), candidates.detach()
+    Qn = torch.empty((Q, D), dtype=torch.float32, device=dev)
+    Cn = torch.empty((max(M, 1), D), dtype=torch.float32, device=dev)
+    _normalize_into(lib, queries, picked[order].contiguous().data_ptr(), Q, Qn.data_ptr(), D, Q, s)
+    _normalize_into(lib, candidates, None, M, Cn.data_ptr(), D, M, s)
+    out_idx = torch.empty((Q, k), dtype=torch.int32, device=dev)
+    out_score = torch.empty((Q, k), dtype=torch.float32, device=dev)
+    out_n = torch.empty(Q, dtype=torch.int32, device=dev)
+    lcnt = torch.empty(Q, dtype=torch.int32, device=dev)
+    slots = max((b - a) * cap for a, b, cap in blocks)  # one pair of list buffers serves every block
+    lkey = torch.empty(slots, dtype=torch.int32, device=dev)
+    lidx = torch.empty(slots, dtype=torch.int32, device=dev)
+    if masks is not None:
+        wh = masks.to(dev)[order].contiguous()
+        attrs = attrs.detach().contiguous()
+    for a, b, cap in blocks:
+        nb = b - a
+        _ffi.check(lib.lgcn_score_lists(Qn.data_ptr() + a * D * 4, nb, Cn.data_ptr(), M, D, aptr.data_ptr(),
+                                        aidx.data_ptr(), arow.data_ptr() + a * 8, aptr.numel() - 1, lkey.data_ptr(),
+                                        lidx.data_ptr(), lcnt.data_ptr() + a * 4, cap, s), "lgcn_score_lists")
+        ex = (None, None, None, 0) if eptr is None else (eptr.data_ptr(), eidx.data_ptr(), erow.data_ptr() + a * 8, ER)
+        outs = (out_idx.data_ptr() + a * k * 4, out_score.data_ptr() + a * k * 4, out_n.data_ptr() + a * 4)
+        if masks is None:
+            _ffi.check(lib.lgcn_select_topk_ranked(lkey.data_ptr(), lidx.data_ptr(), lcnt.data_ptr() + a * 4, _ffi.RANKED_REPEATS,
+                                                   cap, k, nb, nb, *ex, None, *outs, s), "lgcn_select_topk_ranked")
+        else:
+            _ffi.check(lib.lgcn_select_topk_ranked_attr(lkey.data_ptr(), lidx.data_ptr(), lcnt.data_ptr() + a * 4,
+                                                        _ffi.RANKED_REPEATS, cap, k, nb, nb, *ex, None, *outs, attrs.data_ptr(),
+                                                        wh.data_ptr() + a * 12, s), "lgcn_select_topk_ranked_attr")
+    idx = torch.empty_like(out_idx)
+    score = torch.empty_like(out_score)
+    idx[order] = out_idx
+    score[order] = out_score
+    return (idx.to(torch.int64) if index_dtype == torch.int64 else idx), score
+
+
 def topk_rows(queries: torch.Tensor, picked: torch.Tensor, candidates: torch.Tensor, k: int, excl=None,
               cap: int | None = None, subset: int | None = None, index_dtype: torch.dtype = torch.int64,
-              attrs: torch.Tensor | None = None, where=None):
+              attrs: torch.Tensor | None = None, where=None, among=None):
     """(idx [Q, k] of ``index_dtype``, int64 by default; score f32 [Q, k]) on the device: for query
     row queries[picked[q]], the k best rows of ``candidates`` by cosine score that its exclusion row
     does not name, in rank order (score descending, candidate index ascending; NaN first).
@@ -187,12 +334,31 @@ def topk_rows(queries: torch.Tensor, picked: torch.Tensor, candidates: torch.Ten
     not excluded are ranked. Under a filter a query short of k eligible candidates is padded with
     -1 / -inf above ``cap`` too, as long as the candidates that pass for it fit ``cap`` (RuntimeError
     otherwise); the ValueError above is left for M minus the excluded falling below k. topk_items,
-    topk_users, topk_rows_diverse and metrics.evaluate_ranking hand both on."""
+    topk_users, topk_rows_diverse and metrics.evaluate_ranking hand both on.
+    among: None, or a candidate set per query as a CSR, (ptr, idx) — row q is query q's — or
+    (ptr, idx, rows) with rows[q] naming the CSR row of query q (candidate_csr builds one): query q
+    ranks only the entries of its row that lie in [0, M), are not in its excl row and pass ``where``,
+    by the same rule on the same keys, so its list is its full ranking restricted to the row, bit for
+    bit. Entries may come in any order; an entry named twice is ranked twice (two adjacent slots of
+    the list: pass candidate_csr's deduplicated rows to avoid it), an entry outside [0, M) names
+    nothing. A query with fewer than k such entries is padded with -1 / -inf; a missing or empty row
+    gives an all-padding list, never an error. The cost follows the sum of the row lengths, not M:
+    the candidates are normalised once, each row is scored by lgcn_score_lists, no score filter
+    runs. Queries are processed longest row first in blocks whose list capacity is
+    max(k, the block's longest row), at most BLOCK_BYTES // (8 * capacity) queries each, and come
+    back in the caller's order; the row lengths are read on the host once per call. A row longer
+    than _ffi.RANKED_MAX_CAP is a ValueError naming the length; cap= and subset= have no meaning
+    with among and passing either is a ValueError."""
     k = int(k)
     if index_dtype not in (torch.int64, torch.int32):
         raise ValueError(f"recommend: index_dtype must be torch.int64 or torch.int32, got {index_dtype}")
     if k < 1 or k > MAX_K:
         raise ValueError(f"recommend: k={k} outside [1, {MAX_K}]")
+    if among is not None:
+        if cap is not None or subset is not None:
+            raise ValueError("recommend: cap= and subset= have no meaning with among= (a block's capacity is its "
+                             "longest row)")
+        return _topk_among(queries, picked, candidates, k, excl, index_dtype, attrs, where, among)
     cap = CAP if cap is None else int(cap)
     if cap < k:
         raise ValueError(f"recommend: k={k} exceeds the list capacity {cap}")
@@ -392,7 +558,9 @@ def topk_rows_diverse(queries: torch.Tensor, picked: torch.Tensor, candidates: t
     pool: default max(4 * k, 64); whatever is asked for is clamped to what exists and what the
     re-rank kernel holds, min(M, MMR_MAX_POOL, MMR_MAX_LDS_BYTES // (4 * D)) with D the padded
     width, and a pool that ends up below k is a ValueError. excl and kw (cap, subset, index_dtype,
-    attrs, where) are topk_rows'; under a filter a query's pool holds passing candidates only."""
+    attrs, where, among) are topk_rows'; under a filter a query's pool holds passing candidates only,
+    and with among= entries of the query's row only (a pool wider than a row is padded, and the picks
+    all lie in the row)."""
     k, diversity = int(k), _diversity(diversity)
     if k < 1:
         raise ValueError(f"recommend: k={k} outside [1, {MMR_MAX_POOL}]")
@@ -437,16 +605,25 @@ def intra_list_diversity(pair: torch.Tensor, n: torch.Tensor, ks) -> torch.Tenso
     return torch.where(cp >= 2, ild, torch.full((), float("nan"), dtype=f64, device=pair.device))
 
 
-def topk_items(user_emb: torch.Tensor, item_emb: torch.Tensor, users, k: int, seen=None, **kw):
+def topk_items(user_emb: torch.Tensor, item_emb: torch.Tensor, users, k: int, seen=None, among=None, **kw):
     """The k best items for each user index in ``users``; seen: seen_csr(..., by="user") over all
     users (row u is user u's), whose items are left out. Returns topk_rows' (idx, score). kw: topk_rows'
-    cap, subset, index_dtype, attrs and where (the items' attribute words; one filter per user or one for all)."""
+    cap, subset, index_dtype, attrs and where (the items' attribute words; one filter per user or one for all).
+    among: topk_rows' candidate sets with seen's convention — a 2-tuple (ptr, idx) is a CSR over all
+    users, row u being user u's set; a 3-tuple names each query's row."""
     users = torch.as_tensor(users).view(-1)
-    return topk_rows(user_emb, users, item_emb, k, excl=None if seen is None else (seen[0], seen[1], users), **kw)
+    if among is not None and len(among) == 2:
+        among = (among[0], among[1], users)
+    return topk_rows(user_emb, users, item_emb, k, excl=None if seen is None else (seen[0], seen[1], users),
+                     among=among, **kw)
 
 
-def topk_users(user_emb: torch.Tensor, item_emb: torch.Tensor, items, k: int, seen=None, **kw):
+def topk_users(user_emb: torch.Tensor, item_emb: torch.Tensor, items, k: int, seen=None, among=None, **kw):
     """The k best users for each item index in ``items``; seen: seen_csr(..., by="item"); kw as
-    topk_items' (attrs are then the users' attribute words)."""
+    topk_items' (attrs are then the users' attribute words); among: a 2-tuple is a CSR over all items,
+    row i being item i's set of users, a 3-tuple names each query's row."""
     items = torch.as_tensor(items).view(-1)
-    return topk_rows(item_emb, items, user_emb, k, excl=None if seen is None else (seen[0], seen[1], items), **kw)
+    if among is not None and len(among) == 2:
+        among = (among[0], among[1], items)
+    return topk_rows(item_emb, items, user_emb, k, excl=None if seen is None else (seen[0], seen[1], items),
+                     among=among, **kw)

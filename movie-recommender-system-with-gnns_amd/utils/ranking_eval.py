@@ -8,6 +8,9 @@ over every user with held-out items, on the HIP path of lgcn_amd.metrics.
 evaluate_auc reports what the cutoffs hide: exact full-ranking AUC, mean percentile rank, MRR and
 mean rank of the held-out items (lgcn_amd.metrics.evaluate_auc), and the @c metrics at any cutoffs.
 
+evaluate_sampled is the sampled-negative protocol (each user's held-out items ranked among n sampled
+unseen items, HR@10 / NDCG@10), with the negatives drawn and the sets ranked on the device.
+
 evaluate_fold_in does the same for users the model never saw: their support items are folded in
 (lgcn_amd.foldin) and left out, their held-out items are the truth.
 """
@@ -102,3 +105,59 @@ def evaluate_fold_in(model: torch.nn.Module, train_edge_index: torch.Tensor, sup
         support = (support[0].to(device), support[1].to(device))
         rows = foldin.fold_in(support, table, count=degree).rows
         return metrics.evaluate_ranking(rows, item_emb, heldout, ks=ks, seen=support, diversity=diversity, pool=pool)
+
+
+def evaluate_sampled(model: torch.nn.Module, train_edge_index: torch.Tensor, heldout_edge_index: torch.Tensor,
+                     device, negatives: int = 99, ks=(10,), seed: int = 0, embeddings: str = "raw") -> dict:
+    """The sampled-negative protocol (1 + 99, HR@10 / NDCG@10): every user with a held-out edge gets
+    ``negatives`` items drawn uniformly, with replacement, from the items the user has in neither
+    edge set (lgcn_amd.negatives.sample_negatives, one flat draw with the users repeated,
+    reproducible from ``seed``), joined with the user's held-out items into one candidate set
+    (lgcn_amd.recommend.candidate_csr). Draws may repeat and the set is deduplicated, so a user's set
+    holds AT MOST ``negatives`` negatives. The set is ranked with topk_rows' among= and scored
+    against the held-out CSR by lgcn_amd.metrics.rank_metrics / summarize, whose dict comes back with
+    one more key, 'candidates': the mean size of the evaluated users' sets.
+    A user who has every item in one of the edge sets has no unseen item: sample_negatives then draws
+    over all items, and the training items among the draws are left out of the ranking like any other.
+    Edge sets, ``embeddings`` and the device are evaluate_ranking's; the reference's own sampled
+    utils.train_test.evaluate stays as it is."""
+    if embeddings not in ("raw", "propagated"):
+        raise ValueError(f"evaluate_sampled: embeddings must be 'raw' or 'propagated', got {embeddings!r}")
+    negatives = int(negatives)
+    if negatives < 1:
+        raise ValueError(f"evaluate_sampled: negatives={negatives}")
+    from lgcn_amd import metrics
+    from lgcn_amd.negatives import sample_negatives
+    from lgcn_amd.recommend import candidate_csr, seen_csr, topk_rows
+
+    cs = sorted({int(c) for c in ks})  # rank_metrics checks them
+    model.eval()
+    U, I = model.num_users, model.num_items
+    with torch.no_grad():
+        train_edge_index = train_edge_index.to(device)
+        heldout_edge_index = heldout_edge_index.to(device)
+        seen = seen_csr(train_edge_index, U, I, by="user")
+        truth = seen_csr(heldout_edge_index, U, I, by="user")
+        either = seen_csr(torch.cat([train_edge_index, heldout_edge_index], 1), U, I, by="user")
+        if embeddings == "raw":
+            user_emb, item_emb = model.get_embeddings(user_indices=torch.arange(U, device=device),
+                                                      item_indices=torch.arange(I, device=device))
+        else:
+            user_emb, item_emb = model(train_edge_index)
+        held = truth[0][1:] - truth[0][:-1]
+        users = torch.nonzero(held > 0).view(-1)
+        n = users.numel()
+        draws = sample_negatives(users.repeat_interleave(negatives), either, I, seed=seed, step=0)
+        # one padded row per user: the draws, then the held-out items (-1 in the slots a row leaves)
+        width = int(held.max()) if n else 0
+        own = torch.full((n, width), -1, dtype=torch.int64, device=users.device)
+        at = torch.arange(width, device=users.device)[None, :]
+        mine = at < held[users][:, None]
+        own[mine] = truth[1].to(torch.int64)[(truth[0][users][:, None] + at)[mine]]
+        among = candidate_csr(torch.cat([draws.view(n, negatives), own], 1))
+        k = cs[-1]
+        ranked, _ = topk_rows(user_emb, users, item_emb, k, excl=(seen[0], seen[1], users), among=among,
+                              index_dtype=torch.int32)
+        out = metrics.summarize(metrics.rank_metrics(ranked, truth, cs, rows=users), cs)
+        out["candidates"] = float(among[1].numel()) / n if n else float("nan")
+        return out

@@ -19,6 +19,10 @@ lgcn_amd.metrics.rank_positions on the device; ``python utils/recommend.py USER_
 "ten comedies", "anything but horror": the ``genres`` column of movies.csv as one attribute word per
 movie (``genre_table``), tested on the device where the score is tested
 (``python utils/recommend.py USER_ID --genres Comedy,Romance --without Horror``, likewise with ``--movies``).
+``among=`` (recommend_for_users, recommend_for_histories) ranks a given set of movies and nothing else —
+a watchlist, tonight's schedule, another model's shortlist — at the cost of the sets' sizes
+(lgcn_amd.recommend.topk_rows' among; ``python utils/recommend.py USER_ID --among 1,296,318``, likewise
+with ``--movies``).
 Not carried over: the plotting (``visualizations``) and the import-time seeding (nothing here draws
 random numbers). Unknown ids are answered without touching the GPU; everything else needs the model
 on a ROCm device (lgcn_amd._ffi.LgcnError otherwise, there is no CPU fallback).
@@ -26,7 +30,7 @@ How good the served lists are (full-ranking Recall / Precision / HitRate / NDCG 
 rows, training items left out):
     utils.ranking_eval.evaluate_ranking(model, train_data.edge_index, test_data.edge_index, 'cuda', ks=(10, 20))
 """
-from typing import Any, Dict, List, Optional, Sequence, Union
+from typing import Any, Dict, List, Mapping, Optional, Sequence, Union
 
 import torch
 
@@ -108,6 +112,43 @@ def _genre_filter(who: str, handler: Any, genres, genres_all, without_genres):
     return {"attrs": attrs, "where": tuple(masks)}
 
 
+def _among_csr(who: str, among, inputs: int, served, handler: Any, device):
+    """topk_rows' among= of the served queries, {} when among is None. among: a sequence of movie ids
+    shared by every query; a mapping key -> ids; or a sequence of id sequences aligned with the
+    caller's ``inputs`` entries. served: one (position among the inputs, mapping key) per query, in
+    query order. Unknown ids are dropped, an id named twice counts once (candidate_csr)."""
+    if among is None:
+        return {}
+    num_users, movie_id_map = len(handler.user_id_map), handler.movie_id_map
+    known = lambda ids: [movie_id_map[m] - num_users for m in ids if m in movie_id_map]
+    if isinstance(among, Mapping):
+        rows = [known(among.get(key, ())) for _, key in served]
+    else:
+        among = list(among)
+        if among and all(hasattr(x, '__iter__') and not isinstance(x, (str, bytes)) for x in among):
+            if len(among) != inputs:
+                raise ValueError(f"{who}: among holds {len(among)} sets for {inputs} entries")
+            rows = [known(among[slot]) for slot, _ in served]
+        else:  # one set for everybody: one CSR row, named by every query
+            ptr, idx = _rec.candidate_csr([known(among)], device=device)
+            return {"among": (ptr, idx, torch.zeros(len(served), dtype=torch.int64))}
+    return {"among": _rec.candidate_csr(rows, device=device)}
+
+
+def _cli_option(argv: List[str], flag: str) -> Optional[List[str]]:
+    """``--flag A,B`` taken out of the argument list ``argv``: the names, or None when it is absent."""
+    if flag not in argv[1:-1]:
+        return None
+    at = argv.index(flag)
+    names = [x.strip() for x in argv[at + 1].split(',') if x.strip()]
+    del argv[at:at + 2]
+    return names
+
+
+def _cli_ids(names: Optional[List[str]]) -> Optional[List[int]]:
+    return None if names is None else [int(x) for x in names]
+
+
 def _ranked(idx: torch.Tensor, score: torch.Tensor):
     """Host lists of one topk_rows result, the unfilled (-1) slots dropped."""
     idx, score = idx.cpu(), score.cpu()
@@ -162,8 +203,8 @@ def recommend_for_users(model: torch.nn.Module, user_ids: Sequence[int], data_ha
                         exclude_seen: bool = True, train_edge_index: Optional[torch.Tensor] = None,
                         diversity: Optional[float] = None, pool: Optional[int] = None,
                         explain: Optional[int] = None, genres: Optional[Sequence[str]] = None,
-                        genres_all: Optional[Sequence[str]] = None, without_genres: Optional[Sequence[str]] = None
-                        ) -> List[Union[Dict[str, str], List[Dict[str, Any]]]]:
+                        genres_all: Optional[Sequence[str]] = None, without_genres: Optional[Sequence[str]] = None,
+                        among=None) -> List[Union[Dict[str, str], List[Dict[str, Any]]]]:
     """One entry per id of ``user_ids``: the user's k best movies as [{'movie_id', 'title', 'score'}],
     or {'error': 'Invalid user ID'} for an unknown id. With ``exclude_seen`` the movies a user has an
     edge to in ``train_edge_index`` (default: every edge the handler holds, ``data_handler.edge_index``)
@@ -183,7 +224,14 @@ def recommend_for_users(model: torch.nn.Module, user_ids: Sequence[int], data_ha
     ``genres_all`` and none of ``without_genres`` — one filter for the whole call, genre_table's
     attribute words tested on the device (topk_rows' attrs / where). A list is shorter than k when
     fewer movies are left; an unknown name is a ValueError that lists the vocabulary. They combine
-    with ``diversity`` (the pool holds passing movies only) and ``explain``."""
+    with ``diversity`` (the pool holds passing movies only) and ``explain``.
+    ``among`` (None: today's calls) ranks given movies only: a sequence of MovieLens ids shared by every
+    user, a mapping user_id -> ids, or a sequence of id sequences aligned with ``user_ids``. Unknown
+    ids are dropped and an id named twice counts once; a user whose set is empty (or who is missing
+    from the mapping) gets []. The list is the user's full ranking restricted to the set
+    (lgcn_amd.recommend.topk_rows' among, at the cost of the sets' sizes) and combines with
+    ``exclude_seen``, ``diversity`` (the pool holds movies of the set only), ``explain`` and the genre
+    arguments."""
     if diversity is None and pool is not None:
         raise ValueError("recommend_for_users: pool is the re-rank's pool and needs diversity")
     flt = _genre_filter("recommend_for_users", data_handler, genres, genres_all, without_genres)
@@ -201,6 +249,8 @@ def recommend_for_users(model: torch.nn.Module, user_ids: Sequence[int], data_ha
     if flt:
         flt["attrs"] = flt["attrs"].to(dev)
     users = torch.tensor([u for _, u in known], dtype=torch.int64, device=dev)
+    flt.update(_among_csr("recommend_for_users", among, len(user_ids), [(slot, user_ids[slot]) for slot, _ in known],
+                          data_handler, dev))
     excl = history = None
     if exclude_seen or explain is not None:
         ei = data_handler.edge_index if train_edge_index is None else train_edge_index
@@ -238,7 +288,7 @@ def recommend_for_histories(model: torch.nn.Module, histories: Sequence[Sequence
                             diversity: Optional[float] = None, pool: Optional[int] = None,
                             explain: Optional[int] = None, genres: Optional[Sequence[str]] = None,
                             genres_all: Optional[Sequence[str]] = None,
-                            without_genres: Optional[Sequence[str]] = None
+                            without_genres: Optional[Sequence[str]] = None, among=None
                             ) -> List[Union[Dict[str, str], List[Dict[str, Any]]]]:
     """Lists for people the model never saw — someone who has just rated a few films, an anonymous
     session: one entry per history of ``histories`` (each a sequence of MovieLens movie ids), the k
@@ -256,7 +306,9 @@ def recommend_for_histories(model: torch.nn.Module, histories: Sequence[Sequence
     ``exclude_history`` leaves the history's movies out of the list. ``diversity`` / ``pool`` /
     ``explain`` and ``genres`` / ``genres_all`` / ``without_genres`` are recommend_for_users'; the
     'because' movies come from the supplied history (lgcn_amd.explain.explain_rows). All histories are served by one fold-in and one ranking call;
-    if no history has a known id the answer comes without touching the model or the GPU."""
+    if no history has a known id the answer comes without touching the model or the GPU.
+    ``among`` is recommend_for_users': one sequence of ids for every history, a sequence of id sequences
+    aligned with ``histories``, or a mapping from a history's position to its ids."""
     if embeddings not in ("raw", "propagated"):
         raise ValueError(f"recommend_for_histories: embeddings must be 'raw' or 'propagated', got {embeddings!r}")
     if diversity is None and pool is not None:
@@ -289,6 +341,8 @@ def recommend_for_histories(model: torch.nn.Module, histories: Sequence[Sequence
     dev = model.user_embedding.weight.device
     if flt:
         flt["attrs"] = flt["attrs"].to(dev)
+    flt.update(_among_csr("recommend_for_histories", among, len(histories), [(slot, slot) for slot in slots],
+                          data_handler, dev))
     ptr = torch.tensor([0] + [len(r) for r in rows], dtype=torch.int64).cumsum(0).to(dev)
     hidx = torch.tensor([i for r in rows for i in r], dtype=torch.int32, device=dev)
     hw = None if weights is None else torch.tensor([x for r in row_w for x in r], dtype=torch.float32, device=dev)
@@ -375,15 +429,12 @@ if __name__ == '__main__':
     from models.light_gcn import LightGCN
 
     def option(flag):  # --flag A,B taken out of the argument list: the names, or None
-        if flag not in sys.argv[1:-1]:
-            return None
-        at = sys.argv.index(flag)
-        names = [x.strip() for x in sys.argv[at + 1].split(',') if x.strip()]
-        del sys.argv[at:at + 2]
-        return names
+        return _cli_option(sys.argv, flag)
 
-    # a genre filter: --genres Comedy,Romance (any of) --genres-all Comedy,Romance (each of) --without Horror
-    genre_kw = dict(genres=option('--genres'), genres_all=option('--genres-all'), without_genres=option('--without'))
+    # a genre filter: --genres Comedy,Romance (any of) --genres-all Comedy,Romance (each of) --without Horror;
+    # a given set of movies to rank, and nothing else: --among 1,296,318
+    genre_kw = dict(genres=option('--genres'), genres_all=option('--genres-all'), without_genres=option('--without'),
+                    among=_cli_ids(option('--among')))
     filtered = any(v is not None for v in genre_kw.values())
     handler = MovieLensDataHandler('data/movielens-25m/ratings.csv', 'data/movielens-25m/movies.csv')
     model = LightGCN(*handler.get_num_users_items()).to('cuda')
