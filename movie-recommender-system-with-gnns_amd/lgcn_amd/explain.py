@@ -73,9 +73,7 @@ def explain_rows(rec_idx: torch.Tensor, history, candidates: torch.Tensor, r: in
     out_sum = torch.zeros((Q, k), dtype=torch.float32, device=dev)
     if Q == 0 or hidx.numel() == 0:  # nothing to explain with (and no device address to pass)
         return Explained(out_idx.to(index_dtype), out_val, out_n, out_sum)
-    ptr, hidx = ptr.to(dev).contiguous(), hidx.to(dev).contiguous()
-    if hrow is not None:
-        hrow = hrow.to(device=dev, dtype=torch.int64).contiguous()
+    ptr, hidx, hrow = _serving.csr_on(dev, ptr, hidx, hrow)
     if weights is not None:
         weights = weights.detach().contiguous()
     rec_idx, ld = _serving.index_list(rec_idx)

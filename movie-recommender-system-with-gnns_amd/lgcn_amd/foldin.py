@@ -84,9 +84,7 @@ def fold_in_rows(history, table: torch.Tensor, isd: torch.Tensor | None = None,
     out_n = torch.empty(Q, dtype=torch.int32, device=dev)
     if Q == 0 or hidx.numel() == 0 or M == 0:  # nothing to sum (and no device address to pass)
         return FoldedIn(out.zero_(), out_n.zero_())
-    ptr, hidx = ptr.to(dev).contiguous(), hidx.to(dev).contiguous()
-    if hrow is not None:
-        hrow = hrow.to(device=dev, dtype=torch.int64).contiguous()
+    ptr, hidx, hrow = _serving.csr_on(dev, ptr, hidx, hrow)
     table, ldt = _serving.row_view(table.detach())
     isd = None if isd is None else isd.detach().contiguous()
     weights = None if weights is None else weights.detach().contiguous()

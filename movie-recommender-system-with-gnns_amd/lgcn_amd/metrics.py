@@ -85,11 +85,7 @@ def rank_metrics(ranked_idx: torch.Tensor, truth, ks, rows=None) -> RankCounts:
         _ffi.require_device(t, "rank_metrics")
     dev = ranked_idx.device
     ranked_idx, ld = _serving.index_list(ranked_idx)
-    ptr, idx = ptr.contiguous(), idx.contiguous()
-    if idx.numel() == 0:  # every row is empty: the library still wants an address
-        idx = torch.zeros(1, dtype=torch.int32, device=dev)
-    if rows is not None:
-        rows = rows.to(device=dev, dtype=torch.int64).contiguous()
+    ptr, idx, rows = _serving.csr_on(dev, ptr, idx, rows)
     C = len(cs)
     hits = torch.empty((Q, C), dtype=torch.int32, device=dev)
     dcg = torch.empty((Q, C), dtype=torch.float32, device=dev)
@@ -210,17 +206,6 @@ class RankPositions(NamedTuple):
     eligible: torch.Tensor  # int32 [Q]: candidates the query's seen row leaves
 
 
-def _row_lengths(ptr: torch.Tensor, rows: torch.Tensor | None, Q: int) -> torch.Tensor:
-    """int64 [Q]: the length of each query's row of the CSR ptr (rows[q], or q); 0 outside the CSR."""
-    R = ptr.numel() - 1
-    r = torch.arange(Q, device=ptr.device) if rows is None else rows
-    if R == 0:
-        return torch.zeros(Q, dtype=torch.int64, device=ptr.device)
-    inside = (r >= 0) & (r < R)
-    rc = r.clamp(0, R - 1)
-    return torch.where(inside, ptr[rc + 1] - ptr[rc], torch.zeros_like(rc)).clamp(min=0)
-
-
 # truth-row lengths above which queries (sorted longest row first) are issued as a call of their own
 TIER_LENGTHS = (256, 32)
 
@@ -240,16 +225,11 @@ def _issue_positions(lib, tiers, Qn, D, Cn, M, tptr, tidx, trow, sptr, sidx, sro
     """lgcn_rank_positions for each tier's queries: a slice of the query-indexed arrays, the whole of
     the entry-indexed ones (out_ptr holds absolute slots)."""
     for a, b in tiers:
-        at = lambda t, width=8: None if t is None else t.data_ptr() + a * width
-        _ffi.check(lib.lgcn_rank_positions(at(Qn, D * 4), -(-(b - a) // 128) * 128, b - a, Cn.data_ptr(), M, D,
-                                           tptr.data_ptr() + (a * 8 if trow is None else 0),
-                                           tidx.data_ptr() if tidx.numel() else ws.data_ptr(), at(trow),
-                                           tptr.numel() - 1 - (a if trow is None else 0),
-                                           None if sptr is None else sptr.data_ptr() + (a * 8 if srow is None else 0),
-                                           _ffi.ptr(sidx), at(srow),
-                                           0 if sptr is None else sptr.numel() - 1 - (a if srow is None else 0),
-                                           at(out_ptr), nnz, pos.data_ptr(), key.data_ptr(), at(eligible, 4),
-                                           ws.data_ptr(), ws.numel(), stages, stream), "lgcn_rank_positions")
+        _ffi.check(lib.lgcn_rank_positions(Qn.data_ptr() + a * D * 4, _serving.padded(b - a), b - a, Cn.data_ptr(), M, D,
+                                           *_serving.csr_at(tptr, tidx, trow, a), *_serving.csr_at(sptr, sidx, srow, a),
+                                           out_ptr.data_ptr() + a * 8, nnz, pos.data_ptr(), key.data_ptr(),
+                                           eligible.data_ptr() + a * 4, ws.data_ptr(), ws.numel(), stages, stream),
+                   "lgcn_rank_positions")
 
 
 def rank_positions(queries: torch.Tensor, picked, candidates: torch.Tensor, truth, seen=None, rows=None,
@@ -292,14 +272,13 @@ def rank_positions(queries: torch.Tensor, picked, candidates: torch.Tensor, trut
     dev = queries.device
     s = _ffi.stream_of(dev)
     picked = picked.to(device=dev, dtype=torch.int64).contiguous()
-    on = lambda t: None if t is None else t.to(device=dev, dtype=torch.int64).contiguous()
-    tptr, tidx, trow = tptr.to(dev).contiguous(), tidx.to(dev).contiguous(), on(trow)
-    if seen is not None:
-        sptr, sidx, srow = sptr.to(dev).contiguous(), sidx.to(dev).contiguous(), on(srow)
-        if sidx.numel() == 0:  # nothing is seen anywhere (and no device address to pass)
-            sptr = sidx = srow = None
+    tptr, tidx, trow = _serving.csr_on(dev, tptr, tidx, trow)
+    if seen is not None and sidx.numel() == 0:  # nothing is seen anywhere (and no device address to pass)
+        sptr = sidx = srow = None
+    elif seen is not None:
+        sptr, sidx, srow = _serving.csr_on(dev, sptr, sidx, srow)
     out_ptr = torch.zeros(Q + 1, dtype=torch.int64, device=dev)
-    lens = _row_lengths(tptr, trow, Q)
+    lens = _serving.row_lengths(tptr, trow, Q)
     if Q:
         out_ptr[1:] = torch.cumsum(lens, 0)
     nnz, *longer = torch.stack([out_ptr[-1]] + [(lens > n).sum() for n in TIER_LENGTHS]).tolist()  # the host read
@@ -309,11 +288,10 @@ def rank_positions(queries: torch.Tensor, picked, candidates: torch.Tensor, trut
     # order changes no value.
     order = None
     if Q > 128 and nnz:
-        order = torch.sort(lens, descending=True, stable=True).indices
-        ident = torch.arange(Q, device=dev)
-        picked, trow = picked[order], (ident if trow is None else trow)[order].contiguous()
+        order = _serving.longest_first(lens).indices
+        picked, trow = picked[order], _serving.rows_in(order, trow)
         if sptr is not None:
-            srow = (ident if srow is None else srow)[order].contiguous()
+            srow = _serving.rows_in(order, srow)
         given_ptr, out_ptr = out_ptr, torch.zeros_like(out_ptr)
         out_ptr[1:] = torch.cumsum(lens[order], 0)
     pos = torch.empty(nnz, dtype=torch.int32, device=dev)
@@ -332,17 +310,7 @@ def rank_positions(queries: torch.Tensor, picked, candidates: torch.Tensor, trut
             n = torch.where(ok, inside[sptr[(rc + 1).clamp(max=R)]] - inside[sptr[rc]], torch.zeros_like(rc))
             eligible.copy_(M - n)
     elif Q:
-        Dv, qm = ctypes.c_int32(0), ctypes.c_int32(0)
-        _ffi.check(lib.lgcn_recall_width(d, ctypes.byref(Dv), ctypes.byref(qm)), "lgcn_recall_width")
-        D, qmul = Dv.value, qm.value
-        Qpad = (Q + qmul - 1) // qmul * qmul
-        queries = queries.detach()
-        if normalized:
-            Qn = torch.zeros((Qpad, D), dtype=torch.float32, device=dev)
-            Qn[:Q, :d] = queries[picked]
-        else:
-            Qn = torch.empty((Qpad, D), dtype=torch.float32, device=dev)
-            recommend._normalize_into(lib, queries, picked.data_ptr(), Q, Qn.data_ptr(), D, Qpad, s)
+        Qn = _serving.unit_queries(lib, queries, picked, D, _serving.padded(Q), normalized, s)
         Cn = _serving.unit_rows(lib, candidates, D, normalized, s)
         need = ctypes.c_size_t(0)
         _ffi.check(lib.lgcn_rank_positions_workspace_size(Q, nnz, ctypes.byref(need)), "lgcn_rank_positions_workspace_size")
@@ -351,10 +319,9 @@ def rank_positions(queries: torch.Tensor, picked, candidates: torch.Tensor, trut
         _issue_positions(lib, tiers, Qn, D, Cn, M, tptr, tidx, trow, sptr, sidx, srow, out_ptr, nnz, pos, key,
                          eligible, ws, _ffi.RANKPOS_ALL, s)
     if order is not None:  # back to the caller's order: query q's entries start at out_ptr[where q went]
-        went = torch.empty_like(order)
-        went[order] = torch.arange(Q, device=dev)
-        src = torch.repeat_interleave(out_ptr[went] - given_ptr[:-1], lens, output_size=nnz) + torch.arange(nnz, device=dev)
-        pos, key, eligible, out_ptr = pos[src], key[src], eligible[went], given_ptr
+        moved = _serving.in_caller_order(order, out_ptr[:-1]) - given_ptr[:-1]
+        src = torch.repeat_interleave(moved, lens, output_size=nnz) + torch.arange(nnz, device=dev)
+        pos, key, eligible, out_ptr = pos[src], key[src], _serving.in_caller_order(order, eligible), given_ptr
     # the score behind a key (csrc/lgcn_ragged.h ordered_value; key 0, "no key", comes out a NaN)
     bits = torch.where(key < 0, key ^ torch.iinfo(torch.int32).min, ~key)
     return RankPositions(out_ptr, pos, bits.view(torch.float32), eligible)

@@ -18,7 +18,8 @@ import ctypes
 import numpy as np
 import torch
 
-from . import _ffi
+from . import _ffi, _serving
+from ._serving import normalize_into as _normalize_into  # noqa: F401 — the name the GPU tests import
 
 # candidates scored for the first thresholds (≈ k·M/subset survive the filter; lgcn_amd.tuning's
 # recall_subset, default 16384) and the per-query list capacity (>= the subset: the first pass
@@ -45,13 +46,6 @@ class _Workspace:
 
 
 _WS = _Workspace()
-
-
-def _normalize_into(lib, x: torch.Tensor, idx, rows: int, out_ptr: int, D: int, out_rows: int, stream):
-    if x.dim() != 2 or x.dtype != torch.float32 or x.stride(1) != 1:
-        raise TypeError("recall: embeddings must be 2-D fp32 with unit column stride")
-    _ffi.check(lib.lgcn_normalize_rows(x.data_ptr() if x.numel() else None, idx, rows, x.stride(0), x.shape[1],
-                                       out_ptr, D, out_rows, stream), "lgcn_normalize_rows")
 
 
 def topk_hits(users: torch.Tensor, picked: torch.Tensor, pos: torch.Tensor, neg: torch.Tensor, k: int,
@@ -83,17 +77,15 @@ def topk_hits(users: torch.Tensor, picked: torch.Tensor, pos: torch.Tensor, neg:
         raise RuntimeError("selected index k out of range")
     if k > cap:
         raise ValueError(f"recall: k={k} exceeds the list capacity {cap}")
-    Dv, qm = ctypes.c_int32(0), ctypes.c_int32(0)
-    _ffi.check(lib.lgcn_recall_width(d, ctypes.byref(Dv), ctypes.byref(qm)), "lgcn_recall_width")
-    D, qmul = Dv.value, qm.value
+    D, qmul = _serving.width("recall", d), _serving.QUERY_MULTIPLE
     picked = picked.to(device=dev, dtype=torch.int64).contiguous()
     Q = picked.numel()
-    Qpad = max(qmul, (Q + qmul - 1) // qmul * qmul)
+    Qpad = _serving.padded(Q)
     ws = _WS.get(dev, Qpad, M, D, cap)
     s = _ffi.stream_of(dev)
-    _normalize_into(lib, users, picked.data_ptr(), Q, ws.Qn.data_ptr(), D, Qpad, s)
-    _normalize_into(lib, pos, None, P, ws.Cn.data_ptr(), D, P, s)
-    _normalize_into(lib, neg, None, Nn, ws.Cn.data_ptr() + P * D * 4, D, Nn, s)
+    _serving.normalize_into(lib, users, picked.data_ptr(), Q, ws.Qn.data_ptr(), D, Qpad, s)
+    _serving.normalize_into(lib, pos, None, P, ws.Cn.data_ptr(), D, P, s)
+    _serving.normalize_into(lib, neg, None, Nn, ws.Cn.data_ptr() + P * D * 4, D, Nn, s)
     if ties == "cpu":
         return _hits_cpu_ties(lib, ws, M, D, k, P, Q, Qpad, qmul, s)
     # first thresholds: the k-th best of a strided subset (a lower bound of the true k-th best)

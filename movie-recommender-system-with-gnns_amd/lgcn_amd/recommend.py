@@ -24,6 +24,15 @@ any point and the host reads at most one value pair per query block.
                  ranked emit             lgcn_select_topk_ranked[_attr]
     and the list is the query's full ranking restricted to its row, bit for bit.
 
+On the host topk_rows is one prepared plan and three block strategies. It checks every argument
+before the library is loaded, then builds a _Plan: the query order (the caller's, or the among
+sort), Qn and Cn, the output buffers, the exclusion CSR and the attribute table on the device, and
+the only two places that choose between a kernel and its _attr twin (_Plan.filter, _Plan.select).
+_run_dense, _run_filtered and _run_among are the three blocks of the table above, written over the
+plan; _Plan.finish puts the lists back in the caller's order and gives them their index dtype. The
+pieces that other modules need too (row lengths, a CSR argument's device tensors and block
+addresses, unit rows, the padded sizes, the longest-first order) live in _serving.
+
 Ranking rule: score descending, then candidate index ascending (NaN scores first). The threshold
 is formed from eligible subset entries only: it is then the k-th best of a subset of the eligible
 candidates, so it is a lower bound of the k-th best eligible score of all M, and the filtered list
@@ -36,14 +45,12 @@ Diversity on top of relevance (csrc/lgcn_rerank.hip, one wave per query, the poo
 """
 from __future__ import annotations
 
-import ctypes
 import operator
 from typing import NamedTuple
 
 import torch
 
 from . import _ffi, _serving
-from .recall import _normalize_into
 
 # list workspace of one query block (8 bytes per list slot: key + index); follows recall.STL_BLOCK_BYTES
 BLOCK_BYTES = 1 << 30
@@ -80,31 +87,6 @@ def seen_csr(edge_index: torch.Tensor, num_users: int, num_items: int, by: str =
     if R > 0:
         ptr[1:] = torch.cumsum(torch.bincount(key // max(C, 1), minlength=R), 0)
     return ptr, (key % max(C, 1)).to(torch.int32)
-
-
-def _excl_args(excl, dev, Q: int):
-    """(ptr, idx, rows | None, R) of an exclusion argument, checked (_serving.csr_arg) and on the
-    device; all None / 0 when nothing is excluded."""
-    if excl is None:
-        return None, None, None, 0
-    ptr, idx, rows, _ = _serving.csr_arg("recommend", "excl", excl, Q)
-    if idx.numel() == 0:  # nothing to exclude anywhere (and no device address to pass)
-        return None, None, None, 0
-    if rows is not None:
-        rows = rows.to(device=dev, dtype=torch.int64).contiguous()
-    return ptr.to(dev).contiguous(), idx.to(dev).contiguous(), rows, ptr.numel() - 1
-
-
-def _row_lengths(ptr: torch.Tensor, rows, Q: int) -> torch.Tensor:
-    """int64 [Q] on ptr's device: the length of each query's row of the CSR ptr (rows[q], or q); 0 for
-    a row outside the CSR, as in the kernels (lgcn_ragged.h's ragged_row)."""
-    R = ptr.numel() - 1
-    r = torch.arange(Q, device=ptr.device) if rows is None else rows.to(torch.int64)
-    if R == 0:
-        return torch.zeros(Q, dtype=torch.int64, device=ptr.device)
-    inside = (r >= 0) & (r < R)
-    rc = r.clamp(0, R - 1)
-    return torch.where(inside, ptr[rc + 1] - ptr[rc], torch.zeros_like(rc)).clamp(min=0)
 
 
 def attr_bits(labels, vocabulary) -> torch.Tensor:
@@ -228,82 +210,151 @@ def _among_blocks(lengths, k: int, block_bytes: int):
     return blocks
 
 
-def _topk_among(queries, picked, candidates, k: int, excl, index_dtype, attrs, where, among):
-    """topk_rows' among= path: see its docstring."""
-    Q = torch.as_tensor(picked).numel()
-    aptr, aidx, arow, _ = _serving.csr_arg("recommend", "among", among, Q)
-    masks = None
-    if attrs is not None or where is not None:
-        masks = _where_arg(attrs, where, candidates.shape[0], Q)
-    if excl is not None:
-        _serving.csr_arg("recommend", "excl", excl, Q)
-    # longest row first. The one host read of the call: the sorted row lengths, which give every
-    # block's boundaries and capacity at once (and the refusal of a row the selection cannot hold,
-    # before anything is loaded)
-    lens, order = torch.sort(_row_lengths(aptr, None if arow is None else arow.to(aptr.device), Q), descending=True,
-                             stable=True)
-    lengths = lens.cpu().numpy()
-    if Q and int(lengths[0]) > _ffi.RANKED_MAX_CAP:
-        raise ValueError(f"recommend: an among row has {int(lengths[0])} entries, above the ranked selection's "
-                         f"capacity {_ffi.RANKED_MAX_CAP}")
-    blocks = _among_blocks(lengths, k, BLOCK_BYTES)
-    lib = _ffi.load()
-    for t in (queries, candidates) if masks is None else (queries, candidates, attrs):
-        _ffi.require_device(t, "recommend")
-    dev = queries.device
-    d, M = queries.shape[1], candidates.shape[0]
-    if candidates.shape[1] != d:
-        raise ValueError("recommend: queries and candidates must have the same width")
-    D = _serving.width("recommend", d)
-    picked = torch.as_tensor(picked).to(device=dev, dtype=torch.int64).contiguous().view(-1)
-    if Q == 0:
-        return (torch.empty((0, k), dtype=index_dtype, device=dev),
-                torch.empty((0, k), dtype=torch.float32, device=dev))
-    eptr, eidx, erow, ER = _excl_args(excl, dev, Q)
-    aptr, aidx = aptr.to(dev).contiguous(), aidx.to(dev).contiguous()
-    if aidx.numel() == 0:  # every row is empty: the library still wants an address
-        aidx = torch.zeros(1, dtype=torch.int32, device=dev)
-    every = torch.arange(Q, device=dev)
-    arow = every if arow is None else arow.to(device=dev, dtype=torch.int64)
-    order = order.to(dev)
-    arow = arow[order].contiguous()
-    if eptr is not None:
-        erow = (every if erow is None else erow)[order].contiguous()
-    s = _ffi.stream_of(dev)
-    queries, candidates = queries.detach(), candidates.detach()
-    Qn = torch.empty((Q, D), dtype=torch.float32, device=dev)
-    Cn = torch.empty((max(M, 1), D), dtype=torch.float32, device=dev)
-    _normalize_into(lib, queries, picked[order].contiguous().data_ptr(), Q, Qn.data_ptr(), D, Q, s)
-    _normalize_into(lib, candidates, None, M, Cn.data_ptr(), D, M, s)
-    out_idx = torch.empty((Q, k), dtype=torch.int32, device=dev)
-    out_score = torch.empty((Q, k), dtype=torch.float32, device=dev)
-    out_n = torch.empty(Q, dtype=torch.int32, device=dev)
-    lcnt = torch.empty(Q, dtype=torch.int32, device=dev)
-    slots = max((b - a) * cap for a, b, cap in blocks)  # one pair of list buffers serves every block
-    lkey = torch.empty(slots, dtype=torch.int32, device=dev)
-    lidx = torch.empty(slots, dtype=torch.int32, device=dev)
-    if masks is not None:
-        wh = masks.to(dev)[order].contiguous()
-        attrs = attrs.detach().contiguous()
-    for a, b, cap in blocks:
-        nb = b - a
-        _ffi.check(lib.lgcn_score_lists(Qn.data_ptr() + a * D * 4, nb, Cn.data_ptr(), M, D, aptr.data_ptr(),
-                                        aidx.data_ptr(), arow.data_ptr() + a * 8, aptr.numel() - 1, lkey.data_ptr(),
-                                        lidx.data_ptr(), lcnt.data_ptr() + a * 4, cap, s), "lgcn_score_lists")
-        ex = (None, None, None, 0) if eptr is None else (eptr.data_ptr(), eidx.data_ptr(), erow.data_ptr() + a * 8, ER)
-        outs = (out_idx.data_ptr() + a * k * 4, out_score.data_ptr() + a * k * 4, out_n.data_ptr() + a * 4)
-        if masks is None:
-            _ffi.check(lib.lgcn_select_topk_ranked(lkey.data_ptr(), lidx.data_ptr(), lcnt.data_ptr() + a * 4, _ffi.RANKED_REPEATS,
-                                                   cap, k, nb, nb, *ex, None, *outs, s), "lgcn_select_topk_ranked")
+class _Plan:
+    """One topk_rows call, prepared for whichever block strategy runs it: the library, stream and
+    device; D, M, k, Q and the query order (None: the caller's; else the among sort, every per-query
+    array below being in that order); the unit rows Qn [Qpad, D] and Cn (one normalize each); the
+    output buffers [Qpad, k]; the exclusion CSR on the device (eptr None: nothing is excluded, which an
+    empty idx means too); the attribute words and the mask table (wh None: no filter). A strategy
+    brings the list buffers (lists) and issues the two calls a block is made of: filter and select."""
+
+    def __init__(self, lib, queries, picked, candidates, k: int, D: int, Qpad: int, excl, masks, attrs, order=None):
+        dev = queries.device
+        self.lib, self.dev, self.s = lib, dev, _ffi.stream_of(dev)
+        self.k, self.D, self.Q, self.Qpad, self.M, self.order = k, D, picked.numel(), Qpad, candidates.shape[0], order
+        Q, M = self.Q, self.M
+        self.eptr = self.eidx = self.erow = None
+        if excl is not None and excl[1].numel():  # an empty idx: nothing to exclude anywhere
+            self.eptr, self.eidx, self.erow = _serving.csr_on(dev, *excl)
+        if order is not None:
+            picked = picked[order].contiguous()
+            if self.eptr is not None:
+                self.erow = _serving.rows_in(order, self.erow)
+        self.Qn = _serving.unit_queries(lib, queries, picked, D, Qpad, False, self.s)
+        self.Cn = torch.empty((max(M, 1), D), dtype=torch.float32, device=dev)
+        _serving.normalize_into(lib, candidates.detach(), None, M, self.Cn.data_ptr(), D, M, self.s)
+        self.out_idx = torch.empty((Qpad, k), dtype=torch.int32, device=dev)
+        self.out_score = torch.empty((Qpad, k), dtype=torch.float32, device=dev)
+        self.out_n = torch.empty(Qpad, dtype=torch.int32, device=dev)
+        self.wh = self.attrs = None
+        if masks is not None:  # the kernels' [Qpad, 3] table (padding queries' rows are never read) and attribute words
+            if order is not None:
+                self.wh = masks.to(dev)[order].contiguous()
+            else:
+                self.wh = torch.zeros((Qpad, 3), dtype=torch.int32, device=dev)
+                self.wh[:Q] = masks.to(dev)
+            self.attrs = attrs.detach().contiguous()
+
+    def lists(self, slots: int) -> None:
+        """The list workspace (key + index per slot) that filter fills and select reads."""
+        self.lkey = torch.empty(slots, dtype=torch.int32, device=self.dev)
+        self.lidx = torch.empty(slots, dtype=torch.int32, device=self.dev)
+
+    def blocks(self, cap: int) -> list:
+        """[(q0, nb, qv)] of the padded queries in blocks of at most BLOCK_BYTES of list workspace at
+        ``cap`` slots per query (nb queries from q0 on, the first qv of them real), and that workspace."""
+        qmul, Qpad = _serving.QUERY_MULTIPLE, self.Qpad
+        blk = min(Qpad, max(qmul, (BLOCK_BYTES // (8 * cap)) // qmul * qmul))
+        self.lists(blk * cap)
+        # Q >= 1 and Qpad - Q < 128, while a block starts at a multiple of 128 below Qpad (or at 0):
+        # q0 <= Qpad - 128 < Q, so every block holds a real query (qv >= 1)
+        return [(q0, min(blk, Qpad - q0), min(blk, self.Q - q0)) for q0 in range(0, Qpad, blk)]
+
+    def filter(self, q0: int, nb: int, qv: int, n: int, stride: int, cap: int, what: str, thr=None, counts=None) -> None:
+        """Score the block's queries against n candidates ``stride`` apart into the lists: every score
+        in candidate order (thr None), or the scores at or above the thresholds, counted; under an
+        attribute filter only candidates that pass enter a thresholded list."""
+        qptr = self.Qn.data_ptr() + q0 * self.D * 4
+        args = (qptr, nb, qv, self.Cn.data_ptr(), n, stride, self.D, thr, self.lkey.data_ptr(), self.lidx.data_ptr(),
+                counts, cap)
+        if thr is None or self.wh is None:
+            _ffi.check(self.lib.lgcn_score_filter(*args, self.s), what)
         else:
-            _ffi.check(lib.lgcn_select_topk_ranked_attr(lkey.data_ptr(), lidx.data_ptr(), lcnt.data_ptr() + a * 4,
-                                                        _ffi.RANKED_REPEATS, cap, k, nb, nb, *ex, None, *outs, attrs.data_ptr(),
-                                                        wh.data_ptr() + a * 12, s), "lgcn_select_topk_ranked_attr")
-    idx = torch.empty_like(out_idx)
-    score = torch.empty_like(out_score)
-    idx[order] = out_idx
-    score[order] = out_score
-    return (idx.to(torch.int64) if index_dtype == torch.int64 else idx), score
+            _ffi.check(self.lib.lgcn_score_filter_attr(*args, self.attrs.data_ptr(), self.wh.data_ptr() + q0 * 12, self.s),
+                       "lgcn_score_filter_attr")
+
+    def select(self, q0: int, nb: int, qv: int, counts, dense_n: int, cap: int, thr_out=None, emit: bool = False) -> None:
+        """The ranked selection over the block's lists (counts: their lengths; None: dense rows of
+        dense_n), eligible entries only: the k-th best key into thr_out, or the ranked lists into the
+        outputs' rows from q0 on (emit)."""
+        k = self.k
+        ex = _serving.csr_at(self.eptr, self.eidx, self.erow, q0)
+        outs = (self.out_idx.data_ptr() + q0 * k * 4, self.out_score.data_ptr() + q0 * k * 4,
+                self.out_n.data_ptr() + q0 * 4) if emit else (None, None, None)
+        args = (self.lkey.data_ptr(), self.lidx.data_ptr(), counts, dense_n, cap, k, nb, qv, *ex, thr_out, *outs)
+        if self.wh is None:
+            _ffi.check(self.lib.lgcn_select_topk_ranked(*args, self.s), "lgcn_select_topk_ranked")
+        else:
+            _ffi.check(self.lib.lgcn_select_topk_ranked_attr(*args, self.attrs.data_ptr(), self.wh.data_ptr() + q0 * 12,
+                                                             self.s), "lgcn_select_topk_ranked_attr")
+
+    def finish(self, index_dtype):
+        """(idx, score) of the Q real queries, in the caller's order."""
+        idx, score = self.out_idx[:self.Q], self.out_score[:self.Q]
+        if self.order is None:
+            score = score.clone()
+        else:
+            idx, score = _serving.in_caller_order(self.order, idx), _serving.in_caller_order(self.order, score)
+        return (idx.to(torch.int64) if index_dtype == torch.int64 else idx), score
+
+
+def _run_dense(plan: _Plan) -> None:
+    """M <= cap: every score of a block, then the ranked emit. No host read."""
+    M, cap = plan.M, max(plan.M, plan.k)  # a dense row needs M slots
+    for q0, nb, qv in plan.blocks(cap):
+        plan.filter(q0, nb, qv, M, 1, cap, "lgcn_score_filter(dense)")
+        plan.select(q0, nb, qv, None, M, cap, emit=True)
+
+
+def _run_filtered(plan: _Plan, cap: int, subset: int) -> None:
+    """M > cap: first thresholds from a strided subset, then lists of the scores at or above them,
+    tightened while a list overflows (at most 8 rounds). One host read per block and round."""
+    M, k, dev = plan.M, plan.k, plan.dev
+    stride = max(1, -(-M // min(subset, cap)))
+    S = -(-M // stride)
+    blocks = plan.blocks(cap)
+    lcnt = torch.zeros(blocks[0][1], dtype=torch.int32, device=dev)
+    thr = torch.empty(blocks[0][1], dtype=torch.int32, device=dev)
+    # a row outside the CSR excludes nothing, as in the kernel
+    taken = None if plan.eptr is None else _serving.row_lengths(plan.eptr, plan.erow, plan.Q)
+    for q0, nb, qv in blocks:
+        # eligible candidates of the block's poorest query, read with the first overflow check
+        fewest = torch.full((), M, dtype=torch.int64, device=dev) if taken is None else M - taken[q0:q0 + qv].max()
+        # first thresholds: the k-th best eligible entry of a strided subset
+        plan.filter(q0, nb, qv, S, stride, cap, "lgcn_score_filter(subset)")
+        plan.select(q0, nb, qv, None, S, cap, thr_out=thr.data_ptr())
+        for _ in range(8):
+            lcnt.zero_()
+            plan.filter(q0, nb, qv, M, 1, cap, "lgcn_score_filter", thr=thr.data_ptr(), counts=lcnt.data_ptr())
+            longest, few = torch.stack([lcnt[:qv].max().to(torch.int64), fewest]).tolist()  # the block's host read
+            if few < k:
+                raise ValueError(f"recommend: a query has {few} eligible candidates, fewer than k={k} "
+                                 f"(M={M} is above the dense capacity {cap}, which pads such rows)")
+            if longest <= cap:
+                plan.select(q0, nb, qv, lcnt.data_ptr(), 0, cap, emit=True)
+                break
+            # a list overflowed: its kept entries are real candidates, so the k-th best eligible one
+            # among them is a valid, tighter threshold; filter again
+            plan.select(q0, nb, qv, lcnt.data_ptr(), 0, cap, thr_out=thr.data_ptr())
+        else:
+            raise RuntimeError("recommend: candidate lists kept overflowing (scores too concentrated for the capacity"
+                               + ("" if plan.wh is None else f", or more than cap={cap} candidates pass the filter of a "
+                                                             f"query that cannot fill k={k}") + ")")
+
+
+def _run_among(plan: _Plan, among, blocks) -> None:
+    """Each query's own row as its list (queries longest row first, ``blocks`` of _among_blocks), then
+    the ranked emit; unpadded (Qpad == nb). No filter runs and nothing is read on the host here."""
+    aptr, aidx, arow = _serving.csr_on(plan.dev, *among)
+    arow = _serving.rows_in(plan.order, arow)
+    lcnt = torch.empty(plan.Q, dtype=torch.int32, device=plan.dev)
+    plan.lists(max((b - a) * cap for a, b, cap in blocks))  # one pair of list buffers serves every block
+    for a, b, cap in blocks:
+        counts = lcnt.data_ptr() + a * 4
+        _ffi.check(plan.lib.lgcn_score_lists(plan.Qn.data_ptr() + a * plan.D * 4, b - a, plan.Cn.data_ptr(), plan.M, plan.D,
+                                             *_serving.csr_at(aptr, aidx, arow, a), plan.lkey.data_ptr(),
+                                             plan.lidx.data_ptr(), counts, cap, plan.s), "lgcn_score_lists")
+        plan.select(a, b - a, b - a, counts, _ffi.RANKED_REPEATS, cap, emit=True)
 
 
 def topk_rows(queries: torch.Tensor, picked: torch.Tensor, candidates: torch.Tensor, k: int, excl=None,
@@ -354,129 +405,56 @@ def topk_rows(queries: torch.Tensor, picked: torch.Tensor, candidates: torch.Ten
         raise ValueError(f"recommend: index_dtype must be torch.int64 or torch.int32, got {index_dtype}")
     if k < 1 or k > MAX_K:
         raise ValueError(f"recommend: k={k} outside [1, {MAX_K}]")
+    Q = torch.as_tensor(picked).numel()
     if among is not None:
         if cap is not None or subset is not None:
             raise ValueError("recommend: cap= and subset= have no meaning with among= (a block's capacity is its "
                              "longest row)")
-        return _topk_among(queries, picked, candidates, k, excl, index_dtype, attrs, where, among)
-    cap = CAP if cap is None else int(cap)
-    if cap < k:
-        raise ValueError(f"recommend: k={k} exceeds the list capacity {cap}")
-    if cap > _ffi.RANKED_MAX_CAP:
-        raise ValueError(f"recommend: cap={cap} exceeds {_ffi.RANKED_MAX_CAP}")
-    subset = max(SUBSET_MIN, SUBSET_PER_K * k) if subset is None else int(subset)
-    if subset < 1:
-        raise ValueError(f"recommend: subset={subset}")
-    masks = None
-    if attrs is not None or where is not None:
-        masks = _where_arg(attrs, where, candidates.shape[0], torch.as_tensor(picked).numel())
+        among = _serving.csr_arg("recommend", "among", among, Q)[:3]
+    else:
+        cap = CAP if cap is None else int(cap)
+        if cap < k:
+            raise ValueError(f"recommend: k={k} exceeds the list capacity {cap}")
+        if cap > _ffi.RANKED_MAX_CAP:
+            raise ValueError(f"recommend: cap={cap} exceeds {_ffi.RANKED_MAX_CAP}")
+        subset = max(SUBSET_MIN, SUBSET_PER_K * k) if subset is None else int(subset)
+        if subset < 1:
+            raise ValueError(f"recommend: subset={subset}")
+    masks = _where_arg(attrs, where, candidates.shape[0], Q)
+    if excl is not None:
+        excl = _serving.csr_arg("recommend", "excl", excl, Q)[:3]
+    order = blocks = None
+    if among is not None:
+        # longest row first. The one host read of the call: the sorted row lengths, which give every
+        # block's boundaries and capacity at once (and the refusal of a row the selection cannot hold,
+        # before anything is loaded)
+        lens, order = _serving.longest_first(_serving.row_lengths(among[0], among[2], Q))
+        lengths = lens.cpu().numpy()
+        if Q and int(lengths[0]) > _ffi.RANKED_MAX_CAP:
+            raise ValueError(f"recommend: an among row has {int(lengths[0])} entries, above the ranked selection's "
+                             f"capacity {_ffi.RANKED_MAX_CAP}")
+        blocks = _among_blocks(lengths, k, BLOCK_BYTES)
     lib = _ffi.load()
     for t in (queries, candidates) if masks is None else (queries, candidates, attrs):
         _ffi.require_device(t, "recommend")
     dev = queries.device
-    d, M = queries.shape[1], candidates.shape[0]
-    if candidates.shape[1] != d:
+    if candidates.shape[1] != queries.shape[1]:
         raise ValueError("recommend: queries and candidates must have the same width")
-    Dv, qm = ctypes.c_int32(0), ctypes.c_int32(0)
-    _ffi.check(lib.lgcn_recall_width(d, ctypes.byref(Dv), ctypes.byref(qm)), "lgcn_recall_width")
-    D, qmul = Dv.value, qm.value
+    D = _serving.width("recommend", queries.shape[1])
     picked = torch.as_tensor(picked).to(device=dev, dtype=torch.int64).contiguous().view(-1)
-    Q = picked.numel()
-    ptr, eidx, erow, R = _excl_args(excl, dev, Q)
     if Q == 0:
         return (torch.empty((0, k), dtype=index_dtype, device=dev),
                 torch.empty((0, k), dtype=torch.float32, device=dev))
-    Qpad = max(qmul, (Q + qmul - 1) // qmul * qmul)
-    dense = M <= cap
-    if dense:
-        cap = max(M, k)  # a dense row needs M slots
-    s = _ffi.stream_of(dev)
-    queries, candidates = queries.detach(), candidates.detach()
-    Qn = torch.empty((Qpad, D), dtype=torch.float32, device=dev)
-    Cn = torch.empty((max(M, 1), D), dtype=torch.float32, device=dev)
-    _normalize_into(lib, queries, picked.data_ptr(), Q, Qn.data_ptr(), D, Qpad, s)
-    _normalize_into(lib, candidates, None, M, Cn.data_ptr(), D, M, s)
-    out_idx = torch.empty((Qpad, k), dtype=torch.int32, device=dev)
-    out_score = torch.empty((Qpad, k), dtype=torch.float32, device=dev)
-    out_n = torch.empty(Qpad, dtype=torch.int32, device=dev)
-    blk = min(Qpad, max(qmul, (BLOCK_BYTES // (8 * cap)) // qmul * qmul))
-    lkey = torch.empty((blk, cap), dtype=torch.int32, device=dev)
-    lidx = torch.empty((blk, cap), dtype=torch.int32, device=dev)
-    lcnt = torch.zeros(blk, dtype=torch.int32, device=dev)
-    thr = torch.empty(blk, dtype=torch.int32, device=dev)
-    stride = max(1, -(-M // min(subset, cap)))
-    S = -(-M // stride) if M else 0
-    if masks is not None:  # the kernels' [Qpad, 3] table (padding queries' rows are never read) and attribute words
-        wh = torch.zeros((Qpad, 3), dtype=torch.int32, device=dev)
-        wh[:Q] = masks.to(dev)
-        attrs = attrs.detach().contiguous()
-
-    def ranked(q0, nb, qv, counts, dense_n, thr_out, emit):
-        if ptr is None:
-            ex = (None, None, None, 0)
-        elif erow is not None:
-            ex = (ptr.data_ptr(), eidx.data_ptr(), erow.data_ptr() + q0 * 8, R)
-        else:  # row q of the CSR is query q: the block starts at row q0
-            ex = (ptr.data_ptr() + q0 * 8, eidx.data_ptr(), None, R - q0)
-        outs = (out_idx.data_ptr() + q0 * k * 4, out_score.data_ptr() + q0 * k * 4,
-                out_n.data_ptr() + q0 * 4) if emit else (None, None, None)
-        if masks is None:
-            _ffi.check(lib.lgcn_select_topk_ranked(lkey.data_ptr(), lidx.data_ptr(), counts, dense_n, cap, k, nb, qv,
-                                                   *ex, thr_out, *outs, s), "lgcn_select_topk_ranked")
+    if among is not None:  # unpadded: a block is launched for its own queries only
+        plan = _Plan(lib, queries, picked, candidates, k, D, Q, excl, masks, attrs, order.to(dev))
+        _run_among(plan, among, blocks)
+    else:
+        plan = _Plan(lib, queries, picked, candidates, k, D, _serving.padded(Q), excl, masks, attrs)
+        if candidates.shape[0] <= cap:
+            _run_dense(plan)
         else:
-            _ffi.check(lib.lgcn_select_topk_ranked_attr(lkey.data_ptr(), lidx.data_ptr(), counts, dense_n, cap, k, nb,
-                                                        qv, *ex, thr_out, *outs, attrs.data_ptr(),
-                                                        wh.data_ptr() + q0 * 12, s), "lgcn_select_topk_ranked_attr")
-
-    for q0 in range(0, Qpad, blk):
-        nb = min(blk, Qpad - q0)
-        qv = max(0, min(nb, Q - q0))
-        qptr = Qn.data_ptr() + q0 * D * 4
-        if dense:
-            _ffi.check(lib.lgcn_score_filter(qptr, nb, qv, Cn.data_ptr(), M, 1, D, None, lkey.data_ptr(),
-                                             lidx.data_ptr(), None, cap, s), "lgcn_score_filter(dense)")
-            ranked(q0, nb, qv, None, M, None, True)
-            continue
-        if qv == 0:
-            ranked(q0, nb, 0, None, 0, None, True)
-            continue
-        # eligible candidates of the block's poorest query, read with the first overflow check
-        if ptr is None:
-            fewest = torch.full((), M, dtype=torch.int64, device=dev)
-        else:
-            r = erow[q0:q0 + qv] if erow is not None else torch.arange(q0, q0 + qv, device=dev)
-            inside = (r >= 0) & (r < R)  # a row outside the CSR excludes nothing, as in the kernel
-            rc = r.clamp(0, R - 1)
-            fewest = M - torch.where(inside, ptr[rc + 1] - ptr[rc], torch.zeros_like(rc)).max()
-        # first thresholds: the k-th best eligible entry of a strided subset
-        _ffi.check(lib.lgcn_score_filter(qptr, nb, qv, Cn.data_ptr(), S, stride, D, None, lkey.data_ptr(),
-                                         lidx.data_ptr(), None, cap, s), "lgcn_score_filter(subset)")
-        ranked(q0, nb, qv, None, S, thr.data_ptr(), False)
-        for _ in range(8):
-            lcnt.zero_()
-            if masks is None:
-                _ffi.check(lib.lgcn_score_filter(qptr, nb, qv, Cn.data_ptr(), M, 1, D, thr.data_ptr(), lkey.data_ptr(),
-                                                 lidx.data_ptr(), lcnt.data_ptr(), cap, s), "lgcn_score_filter")
-            else:  # only candidates that pass enter a list
-                _ffi.check(lib.lgcn_score_filter_attr(qptr, nb, qv, Cn.data_ptr(), M, 1, D, thr.data_ptr(),
-                                                      lkey.data_ptr(), lidx.data_ptr(), lcnt.data_ptr(), cap,
-                                                      attrs.data_ptr(), wh.data_ptr() + q0 * 12, s),
-                           "lgcn_score_filter_attr")
-            longest, few = torch.stack([lcnt[:qv].max().to(torch.int64), fewest]).tolist()  # the block's host read
-            if few < k:
-                raise ValueError(f"recommend: a query has {few} eligible candidates, fewer than k={k} "
-                                 f"(M={M} is above the dense capacity {cap}, which pads such rows)")
-            if longest <= cap:
-                ranked(q0, nb, qv, lcnt.data_ptr(), 0, None, True)
-                break
-            # a list overflowed: its kept entries are real candidates, so the k-th best eligible one
-            # among them is a valid, tighter threshold; filter again
-            ranked(q0, nb, qv, lcnt.data_ptr(), 0, thr.data_ptr(), False)
-        else:
-            raise RuntimeError("recommend: candidate lists kept overflowing (scores too concentrated for the capacity"
-                               + ("" if masks is None else f", or more than cap={cap} candidates pass the filter of a query "
-                                                           f"that cannot fill k={k}") + ")")
-    return (out_idx[:Q].to(torch.int64) if index_dtype == torch.int64 else out_idx[:Q]), out_score[:Q].clone()
+            _run_filtered(plan, cap, subset)
+    return plan.finish(index_dtype)
 
 
 class Reranked(NamedTuple):

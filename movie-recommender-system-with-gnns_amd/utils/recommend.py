@@ -155,6 +155,51 @@ def _ranked(idx: torch.Tensor, score: torch.Tensor):
     return [[(int(i), float(s)) for i, s in zip(ri.tolist(), rs.tolist()) if i >= 0] for ri, rs in zip(idx, score)]
 
 
+def _check_options(who: str, diversity, pool, explain) -> Optional[int]:
+    """The batch calls' ``pool`` / ``explain`` refusals under the caller's prefix; explain as an int, or None."""
+    if diversity is None and pool is not None:
+        raise ValueError(f"{who}: pool is the re-rank's pool and needs diversity")
+    if explain is None:
+        return None
+    explain = int(explain)
+    if explain < 1 or explain > _explain.MAX_R:
+        raise ValueError(f"{who}: explain={explain} outside [1, {_explain.MAX_R}]")
+    return explain
+
+
+def _serve(handler: Any, out: list, slots: Sequence[int], queries: torch.Tensor, item_emb: torch.Tensor, k: int, excl,
+           diversity, pool, flt: dict, explain=None) -> list:
+    """The batch calls' common end: rank item_emb's rows for the queries (one row per slot of ``slots``;
+    topk_rows, or topk_rows_diverse with ``diversity``), explain the lists (``explain``: None, or a
+    function of the ranked indices that returns lgcn_amd.explain's Explained) and write each query's
+    [{'movie_id', 'title', 'score'[, 'because']}] into ``out`` at its slot. Returns out."""
+    picked = torch.arange(len(slots))
+    with torch.no_grad():
+        if diversity is None:
+            idx, score = _rec.topk_rows(queries, picked, item_emb, k, excl=excl, **flt)
+        else:
+            idx, score = _rec.topk_rows_diverse(queries, picked, item_emb, k, diversity, pool=pool, excl=excl, **flt)[:2]
+        why = None if explain is None else explain(idx)
+    num_users = len(handler.user_id_map)
+    id_movie = _id_map(handler, "id_movie_map", handler.movie_id_map)
+    title_of = _title_of(handler.movies)
+
+    def movie(i: int) -> Dict[str, Any]:
+        return {'movie_id': id_movie[i + num_users], 'title': title_of[id_movie[i + num_users]]}
+
+    idx, score = idx.tolist(), score.tolist()
+    widx, wval = (None, None) if why is None else (why.idx.tolist(), why.value.tolist())
+
+    def because(q: int, j: int) -> Dict[str, Any]:
+        if why is None:
+            return {}
+        return {'because': [dict(movie(b), similarity=v) for b, v in zip(widx[q][j], wval[q][j]) if b >= 0]}
+
+    for q, slot in enumerate(slots):  # the unfilled (-1) slots of a short list are dropped
+        out[slot] = [dict(movie(i), score=s, **because(q, j)) for j, (i, s) in enumerate(zip(idx[q], score[q])) if i >= 0]
+    return out
+
+
 def recommend_from_user(model: torch.nn.Module, user_id: int, data_handler: Any,
                         excluded_train_items: Optional[Union[List[int], torch.Tensor]] = None
                         ) -> Dict[str, Union[str, List[Dict[str, Union[str, float]]]]]:
@@ -232,13 +277,8 @@ def recommend_for_users(model: torch.nn.Module, user_ids: Sequence[int], data_ha
     (lgcn_amd.recommend.topk_rows' among, at the cost of the sets' sizes) and combines with
     ``exclude_seen``, ``diversity`` (the pool holds movies of the set only), ``explain`` and the genre
     arguments."""
-    if diversity is None and pool is not None:
-        raise ValueError("recommend_for_users: pool is the re-rank's pool and needs diversity")
+    explain = _check_options("recommend_for_users", diversity, pool, explain)
     flt = _genre_filter("recommend_for_users", data_handler, genres, genres_all, without_genres)
-    if explain is not None:
-        explain = int(explain)
-        if explain < 1 or explain > _explain.MAX_R:
-            raise ValueError(f"recommend_for_users: explain={explain} outside [1, {_explain.MAX_R}]")
     user_id_map, movie_id_map = data_handler.user_id_map, data_handler.movie_id_map
     num_users, num_items = len(user_id_map), len(movie_id_map)
     out: list = [{'error': 'Invalid user ID'} for _ in user_ids]
@@ -259,27 +299,8 @@ def recommend_for_users(model: torch.nn.Module, user_ids: Sequence[int], data_ha
             excl = (history[0], history[1], users)
     with torch.no_grad():
         user_emb, item_emb = model.get_embeddings(user_indices=users, item_indices=torch.arange(num_items, device=dev))
-        if diversity is None:
-            idx, score = _rec.topk_rows(user_emb, torch.arange(users.numel()), item_emb, k, excl=excl, **flt)
-        else:
-            idx, score = _rec.topk_rows_diverse(user_emb, torch.arange(users.numel()), item_emb, k, diversity,
-                                                pool=pool, excl=excl, **flt)[:2]
-        why = None if explain is None else _explain.explain_items(item_emb, users, idx, history, r=explain)
-    id_movie = _id_map(data_handler, "id_movie_map", movie_id_map)
-    title_of = _title_of(data_handler.movies)
-
-    def movie(i: int) -> Dict[str, Any]:
-        return {'movie_id': id_movie[i + num_users], 'title': title_of[id_movie[i + num_users]]}
-
-    if why is None:
-        for (slot, _), row in zip(known, _ranked(idx, score)):
-            out[slot] = [dict(movie(i), score=s) for i, s in row]
-        return out
-    idx, score, widx, wval = idx.tolist(), score.tolist(), why.idx.tolist(), why.value.tolist()
-    for q, (slot, _) in enumerate(known):
-        out[slot] = [dict(movie(i), score=s, because=[dict(movie(b), similarity=v) for b, v in zip(bi, bv) if b >= 0])
-                     for i, s, bi, bv in zip(idx[q], score[q], widx[q], wval[q]) if i >= 0]
-    return out
+    why = None if explain is None else (lambda idx: _explain.explain_items(item_emb, users, idx, history, r=explain))
+    return _serve(data_handler, out, [slot for slot, _ in known], user_emb, item_emb, k, excl, diversity, pool, flt, why)
 
 
 def recommend_for_histories(model: torch.nn.Module, histories: Sequence[Sequence[int]], data_handler: Any, k: int = 10,
@@ -311,12 +332,7 @@ def recommend_for_histories(model: torch.nn.Module, histories: Sequence[Sequence
     aligned with ``histories``, or a mapping from a history's position to its ids."""
     if embeddings not in ("raw", "propagated"):
         raise ValueError(f"recommend_for_histories: embeddings must be 'raw' or 'propagated', got {embeddings!r}")
-    if diversity is None and pool is not None:
-        raise ValueError("recommend_for_histories: pool is the re-rank's pool and needs diversity")
-    if explain is not None:
-        explain = int(explain)
-        if explain < 1 or explain > _explain.MAX_R:
-            raise ValueError(f"recommend_for_histories: explain={explain} outside [1, {_explain.MAX_R}]")
+    explain = _check_options("recommend_for_histories", diversity, pool, explain)
     if weights is not None and len(weights) != len(histories):
         raise ValueError(f"recommend_for_histories: {len(weights)} weight lists for {len(histories)} histories")
     flt = _genre_filter("recommend_for_histories", data_handler, genres, genres_all, without_genres)
@@ -359,28 +375,9 @@ def recommend_for_histories(model: torch.nn.Module, histories: Sequence[Sequence
             table = _foldin.layer_tables(model.user_embedding.weight, model.item_embedding.weight, model.plan_for(ei),
                                          model.num_layers)[1]
         queries = _foldin.fold_in(history, table, count=degree, weights=hw).rows
-        excl = history if exclude_history else None
-        if diversity is None:
-            idx, score = _rec.topk_rows(queries, torch.arange(len(slots)), item_emb, k, excl=excl, **flt)
-        else:
-            idx, score = _rec.topk_rows_diverse(queries, torch.arange(len(slots)), item_emb, k, diversity,
-                                                pool=pool, excl=excl, **flt)[:2]
-        why = None if explain is None else _explain.explain_rows(idx, history, item_emb, r=explain)
-    id_movie = _id_map(data_handler, "id_movie_map", movie_id_map)
-    title_of = _title_of(data_handler.movies)
-
-    def movie(i: int) -> Dict[str, Any]:
-        return {'movie_id': id_movie[i + num_users], 'title': title_of[id_movie[i + num_users]]}
-
-    if why is None:
-        for slot, row in zip(slots, _ranked(idx, score)):
-            out[slot] = [dict(movie(i), score=s) for i, s in row]
-        return out
-    idx, score, widx, wval = idx.tolist(), score.tolist(), why.idx.tolist(), why.value.tolist()
-    for q, slot in enumerate(slots):
-        out[slot] = [dict(movie(i), score=s, because=[dict(movie(b), similarity=v) for b, v in zip(bi, bv) if b >= 0])
-                     for i, s, bi, bv in zip(idx[q], score[q], widx[q], wval[q]) if i >= 0]
-    return out
+    why = None if explain is None else (lambda idx: _explain.explain_rows(idx, history, item_emb, r=explain))
+    return _serve(data_handler, out, slots, queries, item_emb, k, history if exclude_history else None, diversity, pool,
+                  flt, why)
 
 
 def rank_for_user(model: torch.nn.Module, user_id: int, movie_ids: Sequence[int], data_handler: Any,

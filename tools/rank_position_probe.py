@@ -46,21 +46,19 @@ class Staged:
 
     def __init__(self, lib, user_emb, item_emb, users, truth, seen):
         from lgcn_amd import _ffi, _serving, metrics
-        from lgcn_amd.recall import _normalize_into
 
         dev = user_emb.device
         self.lib, self.s = lib, _ffi.stream_of(dev)
         self.Q, self.M, d = users.numel(), item_emb.shape[0], user_emb.shape[1]
         self.D = _serving.width("probe", d)
-        self.Qpad = -(-self.Q // 128) * 128
+        self.Qpad = _serving.padded(self.Q)
         self.Cn = _serving.unit_rows(lib, item_emb, self.D, False, self.s)
         # longest truth row first, as rank_positions hands its queries over
-        users = users[torch.sort(metrics._row_lengths(truth[0], users, self.Q), descending=True, stable=True).indices]
+        users = users[_serving.longest_first(_serving.row_lengths(truth[0], users, self.Q)).indices]
         self.users, self.truth, self.seen = users, truth, seen
-        self.Qn = torch.empty((self.Qpad, self.D), dtype=torch.float32, device=dev)
-        _normalize_into(lib, user_emb, users.data_ptr(), self.Q, self.Qn.data_ptr(), self.D, self.Qpad, self.s)
+        self.Qn = _serving.unit_queries(lib, user_emb, users, self.D, self.Qpad, False, self.s)
         self.out_ptr = torch.zeros(self.Q + 1, dtype=torch.int64, device=dev)
-        self.out_ptr[1:] = torch.cumsum(metrics._row_lengths(truth[0], users, self.Q), 0)
+        self.out_ptr[1:] = torch.cumsum(_serving.row_lengths(truth[0], users, self.Q), 0)
         lens = self.out_ptr[1:] - self.out_ptr[:-1]
         self.nnz = int(self.out_ptr[-1])
         self.tiers = metrics._tiers(self.Q, [int((lens > n).sum()) for n in metrics.TIER_LENGTHS])
