@@ -935,6 +935,47 @@ int lgcn_score_lists(const float* Qn, int64_t Qvalid, const float* Cn, int64_t M
                      int64_t among_rows, uint32_t* list_key, int32_t* list_idx, int32_t* list_n, int32_t cap,
                      lgcn_stream_t stream);
 
+/* Group recommendation (added under ABI 11, purely additive): one list for several members — "what do
+ * the four of us watch tonight?". lgcn_score_filter_groups is lgcn_score_filter whose queries come in
+ * groups of S rows and whose lists are per GROUP: a candidate's member scores are reduced to one key
+ * before anything is tested or stored, so lgcn_select_topk_ranked[_attr], the exclusion CSR and the
+ * thresholds then serve groups as they serve queries (csrc/lgcn_recall_group.hip; no workspace).
+ *   Qn [Gpad * S, D]: unit rows; group g owns rows [g * S, (g + 1) * S). S is 2, 4, 8, 16 or 32 and
+ *     Gpad * S a multiple of 128. gsize[g] in [0, S] (clamped to it), g < Gvalid: the rows past
+ *     gsize[g] are never part of the result. A group of size 0, and every group of [Gvalid, Gpad),
+ *     takes nothing (in dense mode its row is not written).
+ *   Member m's score s_m for candidate j is exactly the score behind the key lgcn_score_filter gives
+ *     that pair of rows: the same tile, the same steps, in the same order.
+ *   The group's key, to the bit, n = gsize[g], with key(s) the filter's key of a score (an
+ *     order-preserving uint32 image, -0 just below +0, every NaN 0xFFFFFFFF, which ranks first):
+ *       any s_m a NaN:    0xFFFFFFFF, under every aggregate;
+ *       LGCN_GROUP_MIN:   the smallest of key(s_0) .. key(s_{n-1});
+ *       LGCN_GROUP_MAX:   the largest of them (so a -0 orders below a +0 in both);
+ *       LGCN_GROUP_MEAN:  key(sum / (float)n) with sum = s_0, then sum = sum + s_m for m = 1 .. n - 1 in
+ *                         member order, each an IEEE f32 addition, and one IEEE f32 division (nothing
+ *                         fused, nothing re-associated; the library is built with -ffp-contract=off).
+ *                         A sum that is a NaN (+inf and -inf among the members) gives 0xFFFFFFFF too.
+ *     n = 1 gives the member's own key under all three.
+ *   floor: NULL, or f32 [Gvalid]: candidate j is not eligible for group g when s_m < floor[g] for some
+ *     member m (a float comparison: a NaN score does not drop the candidate). List mode only: floor
+ *     with thr NULL is LGCN_E_ARG, as a dense row has no way to say "absent". Under thr[g] = 0 group
+ *     g's list is every candidate that passes the floor.
+ *   thr, list_key, list_idx, list_n, cap, stride: lgcn_score_filter's, per group. thr NULL writes every
+ *     group key at slot r of the group's row (dense mode, M <= cap); otherwise keys >= thr[g] are
+ *     appended (list_n[g] += 1; the caller zeroes list_n; entries past cap are counted, not stored).
+ * No floating-point atomics; bitwise reproducible up to the order within a list.
+ * LGCN_E_ARG: S not one of the five, agg unknown, Gpad * S not a multiple of 128, gsize, list_key or
+ * list_idx NULL, list_n NULL with thr set, floor set with thr NULL, and lgcn_score_filter's own refusals.
+ * Gvalid == 0 or M == 0 returns LGCN_OK without a launch. */
+#define LGCN_GROUP_MIN 0
+#define LGCN_GROUP_MAX 1
+#define LGCN_GROUP_MEAN 2
+#define LGCN_GROUP_MAX_MEMBERS 32
+int lgcn_score_filter_groups(const float* Qn, int64_t Gpad, int64_t Gvalid, int32_t S, const int32_t* gsize,
+                             int32_t agg, const float* floor, const float* Cn, int64_t M, int64_t stride, int32_t D,
+                             const uint32_t* thr, uint32_t* list_key, int32_t* list_idx, int32_t* list_n, int32_t cap,
+                             lgcn_stream_t stream);
+
 /* Host-only (no GPU): `draws` consecutive numpy legacy np.random.choice(n, size, replace=False)
  * calls (reference utils/train_test.py:187) on the MT19937 state (key[624], *pos) of
  * np.random.get_state(), written to out[draws*size]; key/pos are advanced exactly as numpy would

@@ -40,6 +40,8 @@ FOLDIN_LONG = 512  # LGCN_FOLDIN_LONG: history entries above which eight waves s
 FOLDIN_CHUNK = 512  # LGCN_FOLDIN_CHUNK: entries of one wave's chunk of a long history
 NEGATIVES_MAX_N = 32  # LGCN_NEGATIVES_MAX_N
 NEGATIVES_MAX_D = 512  # LGCN_NEGATIVES_MAX_D
+GROUP_MIN, GROUP_MAX, GROUP_MEAN = 0, 1, 2  # LGCN_GROUP_*: lgcn_score_filter_groups' aggregates
+GROUP_MAX_MEMBERS = 32  # LGCN_GROUP_MAX_MEMBERS
 RANKPOS_KEYS, RANKPOS_COUNT, RANKPOS_FINISH, RANKPOS_ALL = 1, 2, 4, 7  # LGCN_RANKPOS_*: lgcn_rank_positions' stages
 
 _lib = None
@@ -160,6 +162,8 @@ _SIGS = {
     "lgcn_rank_positions": ([_vp, _i64, _i64, _vp, _i64, _i32, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _i64,
                              _vp, _vp, _vp, _vp, _sz, _i32, _vp], ctypes.c_int),
     "lgcn_score_lists": ([_vp, _i64, _vp, _i64, _i32, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i32, _vp], ctypes.c_int),
+    "lgcn_score_filter_groups": ([_vp, _i64, _i64, _i32, _vp, _i32, _vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _i32,
+                                  _vp], ctypes.c_int),
     "lgcn_legacy_choice": ([_vp, _vp, _i64, _i64, _i64, _vp], ctypes.c_int),
     "lgcn_slice_schedule_workspace_size": ([_i64, _i64, _i32, _i32, _vp, _vp], ctypes.c_int),
     "lgcn_slice_schedule_build": ([_vp, _vp, _i64, _i64, _vp, _i32, _i32, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp,
@@ -250,7 +254,7 @@ def load(path: os.PathLike | str | None = None) -> ctypes.CDLL:
 CSRC = _HERE.parent / "csrc"
 INCLUDE = _HERE.parent.parent / "include"
 # the translation units of liblgcn.so (lgcn_build.cpp carries the hash and is not hashed)
-SOURCES = ("lgcn_plan.hip", "lgcn_spmm.hip", "lgcn_optim.hip", "lgcn_bpr.hip", "lgcn_recall.hip", "lgcn_recall_attr.hip", "lgcn_recall_among.hip", "lgcn_metrics.hip", "lgcn_rerank.hip",
+SOURCES = ("lgcn_plan.hip", "lgcn_spmm.hip", "lgcn_optim.hip", "lgcn_bpr.hip", "lgcn_recall.hip", "lgcn_recall_attr.hip", "lgcn_recall_among.hip", "lgcn_recall_group.hip", "lgcn_metrics.hip", "lgcn_rerank.hip",
            "lgcn_explain.hip", "lgcn_foldin.hip", "lgcn_negatives.hip", "lgcn_rankpos.hip", "lgcn_rowadam.hip", "lgcn_exchange.hip", "lgcn_partition.cpp", "lgcn_sample.cpp", "lgcn_tuning.cpp", "lgcn_program.cpp")
 # the headers they include (csrc/), hashed and tracked as build dependencies with include/lgcn.h
 HEADERS = ("lgcn_common.h", "lgcn_exact.h", "lgcn_reg.h", "lgcn_ragged.h", "lgcn_scoretile.h", "lgcn_recall_lists.h")

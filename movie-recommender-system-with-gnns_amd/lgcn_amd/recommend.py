@@ -24,6 +24,13 @@ any point and the host reads at most one value pair per query block.
                  ranked emit             lgcn_select_topk_ranked[_attr]
     and the list is the query's full ranking restricted to its row, bit for bit.
 
+    topk_groups (one list for several query rows: "what do the four of us watch tonight?") runs the same
+    dense / filtered blocks with a "query" meaning a group of S member rows (S = 2 .. 32, one plan per size
+    class): lgcn_score_filter_groups (csrc/lgcn_recall_group.hip) reduces a candidate's member scores
+    to ONE key — the minimum (least misery), the maximum (most pleasure) or the mean, with an optional
+    floor no member's score may lie under — before anything is tested or listed, so the lists, the
+    thresholds, the exclusion rows and the ranked selection are the group's.
+
 On the host topk_rows is one prepared plan and three block strategies. It checks every argument
 before the library is loaded, then builds a _Plan: the query order (the caller's, or the among
 sort), Qn and Cn, the output buffers, the exclusion CSR and the attribute table on the device, and
@@ -197,6 +204,90 @@ def candidate_csr(lists, device=None):
     return ptr, (key % C).to(torch.int32)
 
 
+def group_csr(groups, device=None):
+    """The groups of topk_groups as a CSR: (ptr int64 [G + 1], idx int32), row g holding group g's
+    member indices (rows of the query table) in the order given — the order is the association of
+    the "average" strategy's sum — and as often as given: a member named twice counts twice. groups: a
+    sequence of integer sequences (or 1-D tensors), or an integer tensor [G, N] whose negative
+    entries are padding; negative entries are dropped, an empty row stays an empty group. Plain torch
+    ops, on ``device`` (default: the tensor's own, the CPU for sequences)."""
+    if torch.is_tensor(groups):
+        if groups.dim() != 2 or groups.dtype.is_floating_point or groups.dtype.is_complex or groups.dtype == torch.bool:
+            raise TypeError("group_csr: a tensor of groups must be an integer tensor [G, N]")
+        t = groups.detach().to(torch.int64)
+        if device is not None:
+            t = t.to(device)
+        keep = t >= 0
+        lens, cols = keep.sum(1), t[keep]  # boolean indexing walks row by row: member order is kept
+    else:
+        rows = [torch.as_tensor(r).reshape(-1) for r in groups]
+        for r in rows:
+            if r.numel() and (r.dtype.is_floating_point or r.dtype.is_complex or r.dtype == torch.bool):
+                raise TypeError(f"group_csr: member indices must be integers, got {r.dtype}")
+        dev = torch.device("cpu") if device is None else torch.device(device)
+        rows = [r.to(torch.int64) for r in rows]
+        rows = [r[r >= 0] for r in rows]
+        lens = torch.tensor([r.numel() for r in rows], dtype=torch.int64, device=dev)
+        cols = torch.cat(rows + [torch.zeros(0, dtype=torch.int64)]).to(dev)
+    if cols.numel() and int(cols.max()) > torch.iinfo(torch.int32).max:
+        raise ValueError("group_csr: a member index does not fit int32")
+    ptr = torch.zeros(lens.numel() + 1, dtype=torch.int64, device=cols.device)
+    ptr[1:] = torch.cumsum(lens, 0)
+    return ptr, cols.to(torch.int32)
+
+
+def _groups_arg(groups, device=None):
+    """(ptr, idx) of a groups argument: group_csr's own output (ptr int64, idx int32) as it is, anything
+    else through group_csr."""
+    if isinstance(groups, tuple) and len(groups) == 2 and all(torch.is_tensor(t) and t.dim() == 1 for t in groups) \
+            and groups[0].dtype == torch.int64 and groups[1].dtype == torch.int32 and groups[0].numel() >= 1:
+        return groups if device is None else (groups[0].to(device), groups[1].to(device))
+    return group_csr(groups, device=device)
+
+
+def group_seen_csr(seen, groups, by: str = "any"):
+    """The exclusion CSR of groups from the users' seen CSR: (ptr int64 [G + 1], idx int32), row g
+    holding what group g has seen, ascending and deduplicated — by="any": the union of its members'
+    rows (nobody is served something they know), by="all": their intersection (only what everybody
+    knows is left out). seen: seen_csr(..., by="user"), row u being user u's; groups: group_csr's
+    output, or what it takes. A member named twice counts once here; a member with an empty row
+    empties the intersection, and an empty group has an empty row under both. A member outside the
+    seen CSR's rows is a ValueError. Plain torch ops on seen's device: plumbing, not the hot path."""
+    if by not in ("any", "all"):
+        raise ValueError(f"group_seen_csr: by must be 'any' or 'all', got {by!r}")
+    sptr, sidx = _serving.csr_arg("group_seen_csr", "seen", seen)[:2]
+    dev = sptr.device
+    gptr, gidx = _groups_arg(groups, device=dev)
+    G, U = gptr.numel() - 1, sptr.numel() - 1
+    mem = gidx.to(torch.int64)
+    if mem.numel() and (int(mem.min()) < 0 or int(mem.max()) >= U):
+        raise ValueError(f"group_seen_csr: a member index lies outside the seen CSR's {U} rows")
+    grp = torch.repeat_interleave(torch.arange(G, device=dev), gptr[1:] - gptr[:-1])
+    pair = torch.unique(grp * max(U, 1) + mem, sorted=True)  # each (group, member) once
+    grp, mem = pair // max(U, 1), pair % max(U, 1)
+    n = sptr[mem + 1] - sptr[mem]
+    row = torch.repeat_interleave(torch.arange(pair.numel(), device=dev), n)
+    at = sptr[mem][row] + torch.arange(row.numel(), device=dev) - (torch.cumsum(n, 0) - n)[row]
+    items = sidx[at].to(torch.int64)
+    C = int(items.max()) + 1 if items.numel() else 1
+    key, count = torch.unique(grp[row] * C + items, sorted=True, return_counts=True)
+    if by == "all":  # seen rows are deduplicated: the count is the number of members that have the item
+        key = key[count == torch.bincount(grp, minlength=G)[key // C]]
+    ptr = torch.zeros(G + 1, dtype=torch.int64, device=dev)
+    if G > 0:
+        ptr[1:] = torch.cumsum(torch.bincount(key // C, minlength=G), 0)
+    return ptr, (key % C).to(torch.int32)
+
+
+class _Group(NamedTuple):
+    """_Plan's group mode: S member rows per group, the aggregate (_ffi.GROUP_*), the groups' sizes
+    (int32 on the device) and their floors (f32 on the device, or None)."""
+    S: int
+    agg: int
+    size: torch.Tensor
+    floor: torch.Tensor | None
+
+
 def _among_blocks(lengths, k: int, block_bytes: int):
     """[(a, b, capacity)] over queries sorted longest row first (lengths: the sorted row lengths, a
     host sequence): a block's capacity is max(k, its longest row = its first) and it holds at most
@@ -216,12 +307,20 @@ class _Plan:
     array below being in that order); the unit rows Qn [Qpad, D] and Cn (one normalize each); the
     output buffers [Qpad, k]; the exclusion CSR on the device (eptr None: nothing is excluded, which an
     empty idx means too); the attribute words and the mask table (wh None: no filter). A strategy
-    brings the list buffers (lists) and issues the two calls a block is made of: filter and select."""
+    brings the list buffers (lists) and issues the two calls a block is made of: filter and select.
+    Group mode (group: a _Group; topk_groups): a "query" is a group of S member rows. picked then holds
+    S member rows per group, Qn is [Qpad * S, D], Q and Qpad count groups (Qpad a multiple of
+    128 // S), and filter calls lgcn_score_filter_groups; lists, thresholds, the exclusion rows, the
+    mask table and the outputs are per group, and select and the strategies run as they are."""
 
-    def __init__(self, lib, queries, picked, candidates, k: int, D: int, Qpad: int, excl, masks, attrs, order=None):
+    def __init__(self, lib, queries, picked, candidates, k: int, D: int, Qpad: int, excl, masks, attrs, order=None,
+                 group=None, Cn=None):
         dev = queries.device
         self.lib, self.dev, self.s = lib, dev, _ffi.stream_of(dev)
-        self.k, self.D, self.Q, self.Qpad, self.M, self.order = k, D, picked.numel(), Qpad, candidates.shape[0], order
+        self.group, self.rows = group, 1 if group is None else group.S  # member rows per query
+        self.qmul = _serving.QUERY_MULTIPLE // self.rows
+        self.k, self.D, self.Qpad, self.M, self.order = k, D, Qpad, candidates.shape[0], order
+        self.Q = picked.numel() // self.rows
         Q, M = self.Q, self.M
         self.eptr = self.eidx = self.erow = None
         if excl is not None and excl[1].numel():  # an empty idx: nothing to exclude anywhere
@@ -230,9 +329,11 @@ class _Plan:
             picked = picked[order].contiguous()
             if self.eptr is not None:
                 self.erow = _serving.rows_in(order, self.erow)
-        self.Qn = _serving.unit_queries(lib, queries, picked, D, Qpad, False, self.s)
-        self.Cn = torch.empty((max(M, 1), D), dtype=torch.float32, device=dev)
-        _serving.normalize_into(lib, candidates.detach(), None, M, self.Cn.data_ptr(), D, M, self.s)
+        self.Qn = _serving.unit_queries(lib, queries, picked, D, Qpad * self.rows, False, self.s)
+        self.Cn = Cn  # an earlier plan's, over the same candidates (topk_groups: one plan per size class)
+        if Cn is None:
+            self.Cn = torch.empty((max(M, 1), D), dtype=torch.float32, device=dev)
+            _serving.normalize_into(lib, candidates.detach(), None, M, self.Cn.data_ptr(), D, M, self.s)
         self.out_idx = torch.empty((Qpad, k), dtype=torch.int32, device=dev)
         self.out_score = torch.empty((Qpad, k), dtype=torch.float32, device=dev)
         self.out_n = torch.empty(Qpad, dtype=torch.int32, device=dev)
@@ -253,17 +354,37 @@ class _Plan:
     def blocks(self, cap: int) -> list:
         """[(q0, nb, qv)] of the padded queries in blocks of at most BLOCK_BYTES of list workspace at
         ``cap`` slots per query (nb queries from q0 on, the first qv of them real), and that workspace."""
-        qmul, Qpad = _serving.QUERY_MULTIPLE, self.Qpad
+        qmul, Qpad = self.qmul, self.Qpad
         blk = min(Qpad, max(qmul, (BLOCK_BYTES // (8 * cap)) // qmul * qmul))
         self.lists(blk * cap)
-        # Q >= 1 and Qpad - Q < 128, while a block starts at a multiple of 128 below Qpad (or at 0):
-        # q0 <= Qpad - 128 < Q, so every block holds a real query (qv >= 1)
+        if self.group is not None and self.group.floor is not None:  # dense rows become lists: see filter
+            self.fthr = torch.zeros(blk, dtype=torch.int32, device=self.dev)
+            self.fcnt = torch.zeros(blk, dtype=torch.int32, device=self.dev)
+        # Q >= 1 and Qpad - Q < qmul (128 for queries), while a block starts at a multiple of qmul below
+        # Qpad (or at 0): q0 <= Qpad - qmul < Q, so every block holds a real query (qv >= 1)
         return [(q0, min(blk, Qpad - q0), min(blk, self.Q - q0)) for q0 in range(0, Qpad, blk)]
 
     def filter(self, q0: int, nb: int, qv: int, n: int, stride: int, cap: int, what: str, thr=None, counts=None) -> None:
         """Score the block's queries against n candidates ``stride`` apart into the lists: every score
         in candidate order (thr None), or the scores at or above the thresholds, counted; under an
-        attribute filter only candidates that pass enter a thresholded list."""
+        attribute filter only candidates that pass enter a thresholded list.
+        Group mode: the group keys of lgcn_score_filter_groups. It does not know the attribute predicate
+        (select alone applies it), and under a floor "every score" is a list under zero thresholds,
+        counted in fcnt, which select then reads in place of dense rows: a dense row cannot say that a
+        candidate fell under the floor."""
+        if self.group is not None:
+            g = self.group
+            floor = None
+            if g.floor is not None:
+                floor = g.floor.data_ptr() + q0 * 4
+                if thr is None:
+                    self.fcnt.zero_()
+                    thr, counts = self.fthr.data_ptr(), self.fcnt.data_ptr()
+            _ffi.check(self.lib.lgcn_score_filter_groups(
+                self.Qn.data_ptr() + q0 * g.S * self.D * 4, nb, qv, g.S, g.size.data_ptr() + q0 * 4, g.agg, floor,
+                self.Cn.data_ptr(), n, stride, self.D, thr, self.lkey.data_ptr(), self.lidx.data_ptr(), counts, cap,
+                self.s), "lgcn_score_filter_groups")
+            return
         qptr = self.Qn.data_ptr() + q0 * self.D * 4
         args = (qptr, nb, qv, self.Cn.data_ptr(), n, stride, self.D, thr, self.lkey.data_ptr(), self.lidx.data_ptr(),
                 counts, cap)
@@ -278,6 +399,8 @@ class _Plan:
         dense_n), eligible entries only: the k-th best key into thr_out, or the ranked lists into the
         outputs' rows from q0 on (emit)."""
         k = self.k
+        if counts is None and self.group is not None and self.group.floor is not None:
+            counts, dense_n = self.fcnt.data_ptr(), 0  # filter's lists under zero thresholds
         ex = _serving.csr_at(self.eptr, self.eidx, self.erow, q0)
         outs = (self.out_idx.data_ptr() + q0 * k * 4, self.out_score.data_ptr() + q0 * k * 4,
                 self.out_n.data_ptr() + q0 * 4) if emit else (None, None, None)
@@ -455,6 +578,113 @@ def topk_rows(queries: torch.Tensor, picked: torch.Tensor, candidates: torch.Ten
         else:
             _run_filtered(plan, cap, subset)
     return plan.finish(index_dtype)
+
+
+STRATEGIES = {"least_misery": _ffi.GROUP_MIN, "most_pleasure": _ffi.GROUP_MAX, "average": _ffi.GROUP_MEAN}
+
+
+def topk_groups(queries: torch.Tensor, groups, candidates: torch.Tensor, k: int, strategy: str = "least_misery",
+                floor=None, excl=None, cap: int | None = None, subset: int | None = None,
+                index_dtype: torch.dtype = torch.int64, attrs: torch.Tensor | None = None, where=None, among=None):
+    """(idx [G, k] of ``index_dtype``, score f32 [G, k]) on the device: ONE ranked list per group of
+    query rows — "what do the four of us watch tonight?". groups: group_csr's output, or what it
+    takes (lists of member indices into ``queries``, or a padded tensor with -1 padding); at most
+    _ffi.GROUP_MAX_MEMBERS members per group (ValueError naming the size), an empty group gets an
+    all-padding list. A candidate's group score is formed from its members' cosine scores — exactly
+    the scores topk_rows ranks each member by — on the device, before anything is listed
+    (lgcn_score_filter_groups), and the lists are ranked as topk_rows ranks a query's (score
+    descending, candidate index ascending, NaN first; -1 / -inf in the slots a short list cannot fill):
+      strategy="least_misery"   the minimum of the members' scores;
+      strategy="most_pleasure"  the maximum;
+      strategy="average"        the f32 sum of the members' scores in member order, one addition at a
+                                time, over the member count (one f32 division);
+    a NaN member score makes the group's score NaN under all three, and a member named twice counts
+    twice. A group of one has that member's topk_rows list, bit for bit.
+    floor ("average without misery" with strategy="average"; works with every strategy): None, a float
+    for all groups, or one value per group; a candidate that SOME member scores below the group's
+    floor is not eligible (a NaN score is not below anything). NaN is a ValueError. A group left with
+    fewer than k candidates is padded, above ``cap`` too.
+    excl: topk_rows', with one row per GROUP (group_seen_csr builds it from the users' seen rows) or
+    (ptr, idx, rows). cap, subset, index_dtype: topk_rows'. attrs / where: topk_rows' attribute filter
+    with one mask row per group (or one for all); the group filter does not know the predicate — the
+    ranked selection alone applies it — so above ``cap`` candidates a group's list must also hold the
+    non-passing candidates that score above its k-th eligible one, as it must the excluded ones
+    (RuntimeError after eight tightening rounds otherwise; a group that cannot fill k with passing
+    candidates would need all M slots). among= is not supported with groups (ValueError).
+    Groups are bucketed by size class S (the next power of two >= the size, at least 2), one plan run
+    per class over S member rows per group, and come back in the caller's order; the group sizes are
+    read on the host once per call."""
+    k = int(k)
+    if among is not None:
+        raise ValueError("recommend: among= is not supported with groups")
+    if strategy not in STRATEGIES:
+        raise ValueError(f"recommend: strategy must be one of {sorted(STRATEGIES)}, got {strategy!r}")
+    if index_dtype not in (torch.int64, torch.int32):
+        raise ValueError(f"recommend: index_dtype must be torch.int64 or torch.int32, got {index_dtype}")
+    if k < 1 or k > MAX_K:
+        raise ValueError(f"recommend: k={k} outside [1, {MAX_K}]")
+    cap = CAP if cap is None else int(cap)
+    if cap < k:
+        raise ValueError(f"recommend: k={k} exceeds the list capacity {cap}")
+    if cap > _ffi.RANKED_MAX_CAP:
+        raise ValueError(f"recommend: cap={cap} exceeds {_ffi.RANKED_MAX_CAP}")
+    subset = max(SUBSET_MIN, SUBSET_PER_K * k) if subset is None else int(subset)
+    if subset < 1:
+        raise ValueError(f"recommend: subset={subset}")
+    gptr, gidx = (t.cpu() for t in _groups_arg(groups))
+    G = gptr.numel() - 1
+    sizes = gptr[1:] - gptr[:-1]  # the host read of the call: the classes and their padded member rows
+    if G and int(sizes.max()) > _ffi.GROUP_MAX_MEMBERS:
+        raise ValueError(f"recommend: a group has {int(sizes.max())} members, above {_ffi.GROUP_MAX_MEMBERS}")
+    if gidx.numel() and (int(gidx.min()) < 0 or int(gidx.max()) >= queries.shape[0]):
+        raise ValueError(f"recommend: a group member lies outside the {queries.shape[0]} query rows")
+    if floor is not None:
+        floor = torch.as_tensor(floor, dtype=torch.float32).detach().reshape(-1)
+        if floor.numel() not in (1, G):
+            raise ValueError(f"recommend: floor has {floor.numel()} values for {G} groups")
+        if bool(torch.isnan(floor).any()):
+            raise ValueError("recommend: floor is NaN")
+        floor = floor.expand(G)
+    masks = _where_arg(attrs, where, candidates.shape[0], G)
+    if excl is not None:
+        excl = _serving.csr_arg("recommend", "excl", excl, G)[:3]
+    lib = _ffi.load()
+    for t in (queries, candidates) if masks is None else (queries, candidates, attrs):
+        _ffi.require_device(t, "recommend")
+    dev = queries.device
+    if candidates.shape[1] != queries.shape[1]:
+        raise ValueError("recommend: queries and candidates must have the same width")
+    D = _serving.width("recommend", queries.shape[1])
+    out_idx = torch.full((G, k), -1, dtype=torch.int32, device=dev)
+    out_score = torch.full((G, k), float("-inf"), dtype=torch.float32, device=dev)
+    cls = torch.where(sizes > 0, torch.maximum(sizes, torch.full_like(sizes, 2)), torch.zeros_like(sizes))
+    cls = torch.where(cls > 0, 2 ** torch.ceil(torch.log2(cls.clamp(min=1).double())).long(), cls)  # 0: empty
+    Cn = None  # the candidates' unit rows: normalised by the first class's plan, shared by the rest
+    for S in (2, 4, 8, 16, 32):
+        sel = torch.nonzero(cls == S).view(-1)  # the class's groups, in the caller's order
+        Gc = sel.numel()
+        if Gc == 0:
+            continue
+        # [Gc, S] member rows: a group's own in order, its first member in the padding slots (rows the
+        # kernel never takes: it goes by the sizes)
+        slot = torch.arange(S)[None, :]
+        n = sizes[sel][:, None]
+        members = gidx.to(torch.int64)[gptr[sel][:, None] + torch.where(slot < n, slot, torch.zeros_like(slot))]
+        sel_d = sel.to(dev)
+        group = _Group(S, STRATEGIES[strategy], sizes[sel].to(device=dev, dtype=torch.int32).contiguous(),
+                       None if floor is None else floor.to(dev)[sel_d].contiguous())
+        excl_c = None if excl is None else (excl[0], excl[1], sel if excl[2] is None else excl[2].to("cpu")[sel])
+        gm = _serving.QUERY_MULTIPLE // S
+        plan = _Plan(lib, queries, members.reshape(-1).to(dev).contiguous(), candidates, k, D, -(-Gc // gm) * gm, excl_c,
+                     None if masks is None else masks.to(dev)[sel_d], attrs, group=group, Cn=Cn)
+        Cn = plan.Cn
+        if candidates.shape[0] <= cap:
+            _run_dense(plan)
+        else:
+            _run_filtered(plan, cap, subset)
+        idx, score = plan.finish(torch.int32)
+        out_idx[sel_d], out_score[sel_d] = idx, score
+    return (out_idx.to(torch.int64) if index_dtype == torch.int64 else out_idx), out_score
 
 
 class Reranked(NamedTuple):

@@ -23,6 +23,11 @@ movie (``genre_table``), tested on the device where the score is tested
 a watchlist, tonight's schedule, another model's shortlist — at the cost of the sets' sizes
 (lgcn_amd.recommend.topk_rows' among; ``python utils/recommend.py USER_ID --among 1,296,318``, likewise
 with ``--movies``).
+``recommend_for_groups`` / ``recommend_for_group`` serve several users ONE list — "what do the four of us
+watch tonight?" — by least misery (the minimum of the members' scores), most pleasure (the maximum) or
+the average, optionally without anything a member scores under a floor; the members' scores are reduced
+on the device (lgcn_amd.recommend.topk_groups; ``python utils/recommend.py --group 1,5,9 --strategy average
+--floor 0.2``).
 Not carried over: the plotting (``visualizations``) and the import-time seeding (nothing here draws
 random numbers). Unknown ids are answered without touching the GPU; everything else needs the model
 on a ROCm device (lgcn_amd._ffi.LgcnError otherwise, there is no CPU fallback).
@@ -380,6 +385,68 @@ def recommend_for_histories(model: torch.nn.Module, histories: Sequence[Sequence
                   flt, why)
 
 
+def recommend_for_groups(model: torch.nn.Module, groups_of_user_ids: Sequence[Sequence[int]], data_handler: Any,
+                         k: int = 10, strategy: str = "least_misery", floor=None, seen_by: Optional[str] = "any",
+                         genres: Optional[Sequence[str]] = None, genres_all: Optional[Sequence[str]] = None,
+                         without_genres: Optional[Sequence[str]] = None,
+                         train_edge_index: Optional[torch.Tensor] = None
+                         ) -> List[Union[Dict[str, str], List[Dict[str, Any]]]]:
+    """One entry per group of ``groups_of_user_ids`` (each a sequence of user ids, at most 32): the k
+    best movies for the group as a whole, as recommend_for_users' dictionaries [{'movie_id', 'title',
+    'score'}], or {'error': 'Invalid user ID'} where the group names an unknown id; a group of nobody
+    gets []. All groups are ranked by one lgcn_amd.recommend.topk_groups call.
+    ``strategy``: 'least_misery' ranks a movie by the lowest of the members' cosine scores,
+    'most_pleasure' by the highest, 'average' by their mean (summed in the order the members are named;
+    a user named twice counts twice); 'score' is that value. ``floor`` (None, a float, or one value per
+    group): a movie that some member scores below it is left out — 'average' with a floor is "average
+    without misery". ``seen_by``: 'any' leaves out what any member has an edge to in
+    ``train_edge_index`` (default ``data_handler.edge_index``), 'all' only what every member has, None
+    nothing. ``genres`` / ``genres_all`` / ``without_genres`` are recommend_for_users'. A list is shorter
+    than k when fewer movies are left."""
+    if seen_by not in ("any", "all", None):
+        raise ValueError(f"recommend_for_groups: seen_by must be 'any', 'all' or None, got {seen_by!r}")
+    flt = _genre_filter("recommend_for_groups", data_handler, genres, genres_all, without_genres)
+    user_id_map, movie_id_map = data_handler.user_id_map, data_handler.movie_id_map
+    num_users, num_items = len(user_id_map), len(movie_id_map)
+    groups = [list(g) for g in groups_of_user_ids]
+    out: list = [{'error': 'Invalid user ID'} for _ in groups]
+    slots = [slot for slot, g in enumerate(groups) if all(u in user_id_map for u in g)]
+    if not slots:
+        return out
+    members = [[user_id_map[u] for u in groups[slot]] for slot in slots]  # user indices, in the order named
+    if floor is not None and not isinstance(floor, (int, float)):
+        floor = torch.as_tensor(floor, dtype=torch.float32).reshape(-1)
+        if floor.numel() != len(groups):
+            raise ValueError(f"recommend_for_groups: {floor.numel()} floors for {len(groups)} groups")
+        floor = floor[torch.tensor(slots)]
+    dev = model.user_embedding.weight.device
+    if flt:
+        flt["attrs"] = flt["attrs"].to(dev)
+    distinct = sorted({u for g in members for u in g})
+    row_of = {u: r for r, u in enumerate(distinct)}
+    excl = None
+    if seen_by is not None:
+        ei = data_handler.edge_index if train_edge_index is None else train_edge_index
+        excl = _rec.group_seen_csr(_rec.seen_csr(ei.to(dev), num_users, num_items, by="user"), members, by=seen_by)
+    with torch.no_grad():
+        user_emb, item_emb = model.get_embeddings(user_indices=torch.tensor(distinct, dtype=torch.int64, device=dev),
+                                                  item_indices=torch.arange(num_items, device=dev))
+        idx, score = _rec.topk_groups(user_emb, [[row_of[u] for u in g] for g in members], item_emb, k,
+                                      strategy=strategy, floor=floor, excl=excl, **flt)
+    id_movie = _id_map(data_handler, "id_movie_map", movie_id_map)
+    title_of = _title_of(data_handler.movies)
+    for slot, ranked in zip(slots, _ranked(idx, score)):
+        out[slot] = [{'movie_id': id_movie[i + num_users], 'title': title_of[id_movie[i + num_users]], 'score': s}
+                     for i, s in ranked]
+    return out
+
+
+def recommend_for_group(model: torch.nn.Module, user_ids: Sequence[int], data_handler: Any, k: int = 10,
+                        **kw) -> Union[Dict[str, str], List[Dict[str, Any]]]:
+    """recommend_for_groups for one group: its list, or {'error': 'Invalid user ID'}."""
+    return recommend_for_groups(model, [user_ids], data_handler, k=k, **kw)[0]
+
+
 def rank_for_user(model: torch.nn.Module, user_id: int, movie_ids: Sequence[int], data_handler: Any,
                   exclude_seen: bool = True, train_edge_index: Optional[torch.Tensor] = None
                   ) -> Union[Dict[str, str], List[Dict[str, Any]]]:
@@ -433,6 +500,10 @@ if __name__ == '__main__':
     genre_kw = dict(genres=option('--genres'), genres_all=option('--genres-all'), without_genres=option('--without'),
                     among=_cli_ids(option('--among')))
     filtered = any(v is not None for v in genre_kw.values())
+    group = _cli_ids(option('--group'))
+    strategy = (option('--strategy') or ['least_misery'])[0]
+    group_floor = option('--floor')
+    group_floor = None if group_floor is None else float(group_floor[0])
     handler = MovieLensDataHandler('data/movielens-25m/ratings.csv', 'data/movielens-25m/movies.csv')
     model = LightGCN(*handler.get_num_users_items()).to('cuda')
     if os.path.exists('best_model.pth'):
@@ -449,6 +520,19 @@ if __name__ == '__main__':
             if rec['because']:
                 print("   because you watched: " + ", ".join(f"{b['title']} ({b['similarity']:.2f})"
                                                               for b in rec['because']))
+        sys.exit(0)
+    if group is not None:  # one list for several users: --group 1,5,9 [--strategy average] [--floor 0.2]
+        if genre_kw.pop('among') is not None:
+            sys.exit("--among is not supported with --group")
+        train_data, _, _ = handler.get_datasets()
+        served = recommend_for_group(model, group, handler, k=TOP_N, strategy=strategy, floor=group_floor,
+                                     train_edge_index=train_data.edge_index, **genre_kw)
+        if isinstance(served, dict):
+            sys.exit(served['error'])
+        print(f"Top 10 Recommendations for users {', '.join(map(str, group))} together ({strategy}"
+              + ("" if group_floor is None else f", nothing under {group_floor}") + "):")
+        for rank, rec in enumerate(served, 1):
+            print(f"{rank}. {rec['title']} (Score: {rec['score']:.4f})")
         sys.exit(0)
     uid = int(sys.argv[1]) if len(sys.argv) > 1 else next(iter(handler.user_id_map))
     if uid not in handler.user_id_map:
