@@ -813,6 +813,73 @@ int lgcn_foldin_rows(const int64_t* hist_ptr, const int32_t* hist_idx, const flo
                      const float* table, int64_t M, int32_t d, int64_t ldt, const float* isd,
                      float* out, int64_t ldo, int32_t* out_n, lgcn_stream_t stream);
 
+/* Calibrated re-ranking (Steck, RecSys 2018; added under ABI 11, purely additive): lists that keep
+ * the genre mix of the user's own history (csrc/lgcn_calibrate.hip). Genres are the bits of a
+ * candidate's 32-bit attribute word (the words of lgcn_score_filter_attr): LGCN_CALIB_GENRES of them.
+ * An item's own distribution is uniform over its set bits,
+ *     b(g|i) = [bit g of attr[i]] / popcount(attr[i]),
+ * and an item with attr[i] == 0 has no distribution.
+ *
+ * lgcn_attr_profile: a query's target distribution from a ragged history.
+ *   history: CSR (hist_ptr int64[hist_rows + 1], hist_idx int32) with the row conventions of the
+ *     exclusion, truth, explain and fold-in CSRs above: query q uses row hist_row[q] (row q when
+ *     hist_row is NULL); a row outside [0, hist_rows) is empty. Rows may be arbitrarily long; entries
+ *     need be neither sorted nor distinct. hist_w (nullable): one f32 weight per CSR entry, NULL
+ *     meaning 1. attr: uint32[M].
+ *   rule: entry e with i = hist_idx[e] counts when 0 <= i < M, attr[i] != 0 and its weight is > 0
+ *     (a NaN or non-positive weight is skipped); attr is not read for an entry outside [0, M).
+ *     W = sum of w_e over the counting entries; out_p[q, g] = sum_e w_e * b(g|i_e) / W, formed and
+ *     summed in float64 and rounded to f32 once on store (within one f32 ulp of the exact value,
+ *     whatever the order); out_w[q] = W. A row with no counting entry gives 32 zeros and W = 0:
+ *     "no target". out_p is [Q, 32], out_w is [Q].
+ *   No atomics, no workspace. The summation order is a function of the history row's length alone:
+ *   the same history gives the same bits alone or in a batch, at any query position, through
+ *   hist_row or not, and run to run. One wave per history of at most LGCN_PROFILE_LONG entries; the
+ *   eight waves of a workgroup, in a second launch, sum a longer one in chunks of LGCN_PROFILE_CHUNK.
+ * LGCN_E_ARG: a null required pointer (hist_w and hist_row may be NULL), Q, M or hist_rows below 0, Q
+ * above INT32_MAX. Checked before any HIP call; Q == 0 returns LGCN_OK without a launch. Allocates
+ * nothing, reads nothing back, does not synchronise.
+ *
+ * lgcn_rerank_calibrated: k greedy picks from a pool of N, each the best trade of relevance against
+ * the KL divergence between the target and the list's own genre distribution. One wave per query.
+ *   pool_idx[q * ld + p], pool_score[q * ld + p], p < N <= ld: query q's pool in the caller's order
+ *     (lgcn_select_topk_ranked's rank order in practice), entries distinct. A position is eligible
+ *     when 0 <= index < M; anything else (-1 of a short list, any out-of-range value) is skipped and
+ *     its attr is never read (lgcn_rerank_mmr's rule). attr: uint32[M]. target: f32 [Q, 32], row q
+ *     being p (lgcn_attr_profile's out_p in practice).
+ *   state after t picks: mass_g = sum of b(g|i) over the picks, m = the picks with a non-zero word,
+ *     q_g = mass_g / max(1, m), q~_g = (1 - alpha) * q_g + alpha * p_g, and
+ *       KL = sum over the g with p_g > 0 of p_g * ln(p_g / q~_g).
+ *   step t = 0 .. k - 1: the value of an eligible, not yet picked position c is
+ *     (1 - lambda) * r_c - lambda * KL(picks + c) in f32 (NaN counts as -inf); the pick has the
+ *     largest value, the lowest pool position among equal values. out_idx[q, t] = its index,
+ *     out_score[q, t] = r_c bit for bit, out_kl[q, t] = the KL of the list including it.
+ *     With no eligible position left, slots t .. k - 1 get -1 / -inf / 0. out_n[q] = filled slots.
+ *   So: lambda = 0 returns the pool's first k eligible entries (a pool in rank order); the list for
+ *   k' < k is the prefix of the list for k; a target row of zeros returns the pool order with
+ *   out_kl = 0; and two positions with the same word and the same score bits have equal values at
+ *   every step — the value is a function of (score, word, state) only — so ties resolve by position
+ *   and the call is bitwise reproducible.
+ *   The association of the f32 sum and the implementation of the log are not specified; every value
+ *   and KL lies within 64 * 2^-24 of its scale,
+ *     (1 - lambda) * |r_c| + lambda * (sum_g p_g + sum_{p_g > 0} p_g * (|ln p_g| + |ln q~_g|)),
+ *   of the float64 one (tests/calibrate_checker.py). out_idx, out_score, out_kl are [Q, k], out_n [Q].
+ * LGCN_E_ARG: a null pointer, k outside [1, N], N > ld, Q < 0, M < 0, Q above INT32_MAX, lambda
+ * outside [0, 1] or NaN, alpha outside (0, 1) or NaN. LGCN_E_UNSUPPORTED: N > LGCN_CALIB_MAX_POOL.
+ * Checked before any HIP call; Q == 0 returns LGCN_OK without a launch. Allocates nothing, does not
+ * synchronise. */
+#define LGCN_CALIB_GENRES 32      /* genres: the bits of an attribute word */
+#define LGCN_CALIB_MAX_POOL 1024  /* pool entries per query (LGCN_RANKED_MAX_K) */
+#define LGCN_PROFILE_LONG 512     /* history entries above which eight waves share a history */
+#define LGCN_PROFILE_CHUNK 512    /* entries of one wave's chunk of a long history */
+int lgcn_attr_profile(const int64_t* hist_ptr, const int32_t* hist_idx, const float* hist_w,
+                      const int64_t* hist_row, int64_t hist_rows, int64_t Q, const uint32_t* attr, int64_t M,
+                      float* out_p, float* out_w, lgcn_stream_t stream);
+int lgcn_rerank_calibrated(const int32_t* pool_idx, const float* pool_score, int64_t ld, int32_t N, int64_t Q,
+                           const uint32_t* attr, int64_t M, const float* target, int32_t k, float lambda,
+                           float alpha, int32_t* out_idx, float* out_score, float* out_kl, int32_t* out_n,
+                           lgcn_stream_t stream);
+
 /* BPR negatives (added under ABI 11, purely additive): per triplet b < B one item its user has no
  * train edge to, drawn exactly uniformly over the unseen items without rejection (n == 1), or the
  * one of n such draws the model scores highest (dynamic negative sampling, n > 1)

@@ -33,6 +33,10 @@ RANKED_REPEATS = -1  # LGCN_RANKED_REPEATS: dense_n beside list_n for lists that
 METRICS_MAX_CUTOFFS = 8  # LGCN_METRICS_MAX_CUTOFFS
 MMR_MAX_POOL = 512  # LGCN_MMR_MAX_POOL
 MMR_MAX_LDS_BYTES = 131072  # LGCN_MMR_MAX_LDS_BYTES
+CALIB_GENRES = 32  # LGCN_CALIB_GENRES: the bits of an attribute word
+CALIB_MAX_POOL = 1024  # LGCN_CALIB_MAX_POOL
+PROFILE_LONG = 512  # LGCN_PROFILE_LONG: history entries above which eight waves share a history
+PROFILE_CHUNK = 512  # LGCN_PROFILE_CHUNK: entries of one wave's chunk of a long history
 EXPLAIN_MAX_K = 64  # LGCN_EXPLAIN_MAX_K
 EXPLAIN_MAX_R = 8  # LGCN_EXPLAIN_MAX_R
 FOLDIN_MAX_D = 256  # LGCN_FOLDIN_MAX_D
@@ -156,6 +160,9 @@ _SIGS = {
     "lgcn_explain_topr": ([_vp, _i64, _i32, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp,
                            _vp], ctypes.c_int),
     "lgcn_foldin_rows": ([_vp, _vp, _vp, _vp, _i64, _i64, _vp, _i64, _i32, _i64, _vp, _vp, _i64, _vp, _vp], ctypes.c_int),
+    "lgcn_attr_profile": ([_vp, _vp, _vp, _vp, _i64, _i64, _vp, _i64, _vp, _vp, _vp], ctypes.c_int),
+    "lgcn_rerank_calibrated": ([_vp, _vp, _i64, _i32, _i64, _vp, _i64, _vp, _i32, _f32, _f32, _vp, _vp, _vp, _vp, _vp],
+                               ctypes.c_int),
     "lgcn_sample_negatives": ([_vp, _i64, _i64, _vp, _vp, _i64, _i64, ctypes.c_uint64, _i64, _i32, _vp, _i64, _i64, _vp,
                                _i64, _i32, _vp, _vp, _vp, _vp], ctypes.c_int),
     "lgcn_rank_positions_workspace_size": ([_i64, _i64, ctypes.POINTER(_sz)], ctypes.c_int),
@@ -255,7 +262,7 @@ CSRC = _HERE.parent / "csrc"
 INCLUDE = _HERE.parent.parent / "include"
 # the translation units of liblgcn.so (lgcn_build.cpp carries the hash and is not hashed)
 SOURCES = ("lgcn_plan.hip", "lgcn_spmm.hip", "lgcn_optim.hip", "lgcn_bpr.hip", "lgcn_recall.hip", "lgcn_recall_attr.hip", "lgcn_recall_among.hip", "lgcn_recall_group.hip", "lgcn_metrics.hip", "lgcn_rerank.hip",
-           "lgcn_explain.hip", "lgcn_foldin.hip", "lgcn_negatives.hip", "lgcn_rankpos.hip", "lgcn_rowadam.hip", "lgcn_exchange.hip", "lgcn_partition.cpp", "lgcn_sample.cpp", "lgcn_tuning.cpp", "lgcn_program.cpp")
+           "lgcn_explain.hip", "lgcn_foldin.hip", "lgcn_calibrate.hip", "lgcn_negatives.hip", "lgcn_rankpos.hip", "lgcn_rowadam.hip", "lgcn_exchange.hip", "lgcn_partition.cpp", "lgcn_sample.cpp", "lgcn_tuning.cpp", "lgcn_program.cpp")
 # the headers they include (csrc/), hashed and tracked as build dependencies with include/lgcn.h
 HEADERS = ("lgcn_common.h", "lgcn_exact.h", "lgcn_reg.h", "lgcn_ragged.h", "lgcn_scoretile.h", "lgcn_recall_lists.h")
 

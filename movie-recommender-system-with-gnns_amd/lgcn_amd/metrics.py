@@ -18,6 +18,9 @@ each averaged over the users with T > 0 (``users`` in the result).
 With evaluate_ranking(diversity=...) the lists are recommend.topk_rows_diverse's (greedy MMR over a
 relevance pool) and the result also carries ild@c, the mean intra-list diversity
 (recommend.intra_list_diversity) over the evaluated users with at least two listed items.
+With evaluate_ranking(calibration=...) they are recommend.topk_rows_calibrated's (a greedy re-rank towards
+the genre mix of the user's history) and the result carries ckl@c, the mean KL divergence between that mix
+and the list's (recommend.miscalibration) over the evaluated users with a non-zero target.
 
 Below the cutoff (no cap of 1,024, no lists): rank_positions gives every (user, held-out item) pair
 its exact 0-based position in the user's full ranking (lgcn_rank_positions, csrc/lgcn_rankpos.hip:
@@ -144,7 +147,8 @@ def summarize(counts, ks) -> dict:
 
 
 def evaluate_ranking(user_emb: torch.Tensor, item_emb: torch.Tensor, truth, ks=(20,), seen=None, users=None,
-                     diversity: float | None = None, pool: int | None = None, **topk_kw) -> dict:
+                     diversity: float | None = None, pool: int | None = None, calibration: float | None = None,
+                     attrs: torch.Tensor | None = None, history=None, **topk_kw) -> dict:
     """Full-ranking evaluation of an embedding pair: summarize's dict.
 
     truth: the held-out CSR over all users, (ptr, idx) as recommend.seen_csr(heldout_edges, U, I)
@@ -166,12 +170,34 @@ def evaluate_ranking(user_emb: torch.Tensor, item_emb: torch.Tensor, truth, ks=(
     (its default when None) re-ranked by greedy MMR down to max(ks); 0.0 keeps the relevance lists
     and only measures — and the result also carries 'ild@c' for every cutoff: the mean of
     recommend.intra_list_diversity over the evaluated users (non-empty truth row) with at least two
-    listed items, nan when there is none. One more host read."""
+    listed items, nan when there is none. One more host read.
+
+    calibration: None as above. A float in [0, 1] evaluates what recommend.topk_rows_calibrated serves
+    — each user's pool of ``pool`` entries re-ranked towards the genre mix of the user's history;
+    0.0 keeps the relevance lists and only measures — and the result also carries 'ckl@c' for every
+    cutoff: the mean of recommend.miscalibration (KL between the history's genre distribution and the
+    list's) over the evaluated users whose target is non-zero, nan when there is none. attrs: the
+    items' attribute words (int32 [M] on the device; needed, and shared with a where= filter);
+    history: the CSR over all users the targets are profiled from (default: ``seen``). One re-rank per
+    call: calibration together with diversity is a ValueError. One more host read."""
     cs = _cutoffs(ks)
-    if diversity is None and pool is not None:
+    if calibration is not None and diversity is not None:
+        raise ValueError("evaluate_ranking: calibration and diversity are two re-ranks; one per call")
+    if diversity is None and calibration is None and pool is not None:
         raise ValueError("evaluate_ranking: pool is the re-rank's pool and needs diversity")
     if diversity is not None:
         diversity = recommend._diversity(diversity)
+    if calibration is not None:
+        calibration = recommend._calibration(calibration)
+        history = seen if history is None else history
+        if history is None:
+            raise ValueError("evaluate_ranking: calibration needs history= or seen= (what the targets are profiled from)")
+        if attrs is None:
+            raise ValueError("evaluate_ranking: calibration needs attrs (the items' attribute words)")
+    elif history is not None:
+        raise ValueError("evaluate_ranking: history is the calibration's and needs calibration")
+    elif attrs is not None:
+        topk_kw["attrs"] = attrs
     _ffi.require_device(user_emb, "evaluate_ranking")
     dev = user_emb.device
     ptr, idx = truth[0].to(dev), truth[1].to(dev)
@@ -193,6 +219,20 @@ def evaluate_ranking(user_emb: torch.Tensor, item_emb: torch.Tensor, truth, ks=(
         flat = torch.cat([sums, listed.sum(0).to(ild.dtype)]).tolist()  # the host read
         for j, cv in enumerate(cs):
             out[f"ild@{cv}"] = flat[j] / flat[len(cs) + j] if flat[len(cs) + j] else float("nan")
+        return out
+    if calibration is not None:
+        excl = None if seen is None else (seen[0], seen[1], users)
+        target, weight = recommend.attr_profile((history[0], history[1], users), attrs)
+        lists = recommend.topk_rows_calibrated(user_emb, users, item_emb, cs[-1], calibration, attrs=attrs, target=target,
+                                               pool=pool, excl=excl, index_dtype=torch.int32, **topk_kw)
+        counts = rank_metrics(lists.idx, (ptr, idx), cs, rows=users)
+        out = summarize(counts, cs)
+        ckl = recommend.miscalibration(lists.kl, lists.n, cs)
+        listed = ((counts.n_truth > 0) & (weight > 0))[:, None] & ~torch.isnan(ckl)
+        sums = torch.where(listed, ckl, torch.zeros((), dtype=ckl.dtype, device=dev)).sum(0)
+        flat = torch.cat([sums, listed.sum(0).to(ckl.dtype)]).tolist()  # the host read
+        for j, cv in enumerate(cs):
+            out[f"ckl@{cv}"] = flat[j] / flat[len(cs) + j] if flat[len(cs) + j] else float("nan")
         return out
     ranked, _ = recommend.topk_items(user_emb, item_emb, users, cs[-1], seen=seen, index_dtype=torch.int32, **topk_kw)
     return summarize(rank_metrics(ranked, (ptr, idx), cs, rows=users), cs)

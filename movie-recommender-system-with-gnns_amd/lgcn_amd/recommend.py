@@ -49,6 +49,13 @@ Diversity on top of relevance (csrc/lgcn_rerank.hip, one wave per query, the poo
     rerank_mmr            greedy Maximal Marginal Relevance over per-query pools   lgcn_rerank_mmr
     topk_rows_diverse     topk_rows for a pool, then rerank_mmr down to k
     intra_list_diversity  ILD@c from rerank_mmr's pair sums (plain torch)
+
+Calibration on top of relevance (csrc/lgcn_calibrate.hip; Steck, RecSys 2018): lists that keep the
+genre mix of the user's own history, genres being the bits of the attribute words of ``attrs=``.
+    attr_profile          a history CSR -> the target distribution p [Q, 32]      lgcn_attr_profile
+    rerank_calibrated     greedy (1 - l) * relevance - l * KL(p || list) picks    lgcn_rerank_calibrated
+    topk_rows_calibrated  topk_rows for a pool, then rerank_calibrated down to k
+    miscalibration        C_KL@c from rerank_calibrated's KL column (plain torch)
 """
 from __future__ import annotations
 
@@ -71,6 +78,9 @@ MAX_K = _ffi.RANKED_MAX_K
 # the re-rank kernel's pool: entries per query, and bytes of pool rows (N * D * 4) it stages in LDS
 MMR_MAX_POOL = _ffi.MMR_MAX_POOL
 MMR_MAX_LDS_BYTES = _ffi.MMR_MAX_LDS_BYTES
+# the calibrated re-rank: genres (bits of an attribute word) and pool entries per query
+CALIB_GENRES = _ffi.CALIB_GENRES
+CALIB_MAX_POOL = _ffi.CALIB_MAX_POOL
 
 
 def seen_csr(edge_index: torch.Tensor, num_users: int, num_items: int, by: str = "user"):
@@ -811,6 +821,190 @@ def intra_list_diversity(pair: torch.Tensor, n: torch.Tensor, ks) -> torch.Tenso
     pairs = (cp * (cp - 1)).to(f64)
     ild = 1.0 - 2.0 * csum.gather(1, cp) / pairs.clamp(min=1.0)
     return torch.where(cp >= 2, ild, torch.full((), float("nan"), dtype=f64, device=pair.device))
+
+
+class Calibrated(NamedTuple):
+    """lgcn_rerank_calibrated's outputs for Q queries and k picks, on the device."""
+    idx: torch.Tensor    # [Q, k], the pool's index dtype: the picks in pick order, -1 in unfilled slots
+    score: torch.Tensor  # f32 [Q, k]: each pick's relevance as the pool gave it, -inf in unfilled slots
+    kl: torch.Tensor     # f32 [Q, k]: KL(target || the list up to and including the pick), 0 in unfilled slots
+    n: torch.Tensor      # int32 [Q]: filled slots
+
+
+def _calibration(calibration) -> float:
+    c = float(calibration)
+    if not 0.0 <= c <= 1.0:  # NaN fails both comparisons
+        raise ValueError(f"recommend: calibration={c} outside [0, 1]")
+    return c
+
+
+def _alpha(alpha) -> float:
+    a = float(alpha)
+    if not 0.0 < a < 1.0:
+        raise ValueError(f"recommend: alpha={a} outside (0, 1)")
+    return a
+
+
+def _attr_words(who: str, attrs, M: int | None = None) -> None:
+    if not isinstance(attrs, torch.Tensor) or attrs.dtype != torch.int32 or attrs.dim() != 1:
+        raise TypeError(f"{who}: attrs must be an int32 tensor [M] (see attr_bits)")
+    if M is not None and attrs.numel() != M:
+        raise ValueError(f"{who}: attrs has {attrs.numel()} entries for {M} candidates")
+
+
+def attr_profile(history, attrs: torch.Tensor, rows=None, weights: torch.Tensor | None = None):
+    """(p f32 [Q, 32], w f32 [Q]) on the device: each history's target distribution over the 32 bits
+    of the attribute words (lgcn_attr_profile). An item's own distribution is uniform over the set
+    bits of attrs[i]; p is the weighted mean of those of the history's items, formed in float64 and
+    rounded once, w the weight it was formed from. An entry outside [0, M), one whose word is 0
+    (movies.csv's "(no genres listed)") or whose weight is not > 0 (NaN included) is skipped; a
+    history with nothing left gives 32 zeros and w = 0, which rerank_calibrated reads as "no target".
+
+    history: the CSR (ptr int64 [R + 1], idx int32) — one output row per CSR row — or (ptr, idx, rows);
+    rows= names the CSR row of each output beside a 2-tuple (a row outside the CSR is an empty
+    history). attrs: int32 [M] on the device (attr_bits). weights: f32, one per CSR entry; None: 1.
+    The same history gives the same bits alone or in a batch, at any position, and run to run.
+    ValueError / TypeError for bad arguments before anything is loaded."""
+    if rows is not None:
+        if history is None or len(history) != 2:
+            raise ValueError("attr_profile: rows= goes with a history of (ptr, idx)")
+        history = (history[0], history[1], rows)
+    ptr, hidx, hrow, Q = _serving.csr_arg("attr_profile", "history", history)
+    _attr_words("attr_profile", attrs)
+    _serving.check_weights("attr_profile", weights, hidx.numel())
+    lib = _ffi.load()
+    for t in (attrs,) + (() if weights is None else (weights,)):
+        _ffi.require_device(t, "attr_profile")
+    dev = attrs.device
+    p = torch.empty((Q, CALIB_GENRES), dtype=torch.float32, device=dev)
+    w = torch.empty(Q, dtype=torch.float32, device=dev)
+    M = attrs.numel()
+    if Q == 0 or hidx.numel() == 0 or M == 0:  # nothing to sum (and no device address to pass)
+        return p.zero_(), w.zero_()
+    ptr, hidx, hrow = _serving.csr_on(dev, ptr, hidx, hrow)
+    weights = None if weights is None else weights.detach().contiguous()
+    _ffi.check(lib.lgcn_attr_profile(ptr.data_ptr(), hidx.data_ptr(), _ffi.ptr(weights), _ffi.ptr(hrow), ptr.numel() - 1,
+                                     Q, attrs.detach().contiguous().data_ptr(), M, p.data_ptr(), w.data_ptr(),
+                                     _ffi.stream_of(dev)), "lgcn_attr_profile")
+    return p, w
+
+
+def rerank_calibrated(pool_idx: torch.Tensor, pool_score: torch.Tensor, attrs: torch.Tensor, target: torch.Tensor,
+                      k: int, calibration: float, alpha: float = 0.01) -> Calibrated:
+    """Greedy calibrated re-ranking over per-query pools, on the device (lgcn_rerank_calibrated).
+
+    pool_idx [Q, N] int32 or int64 and pool_score [Q, N] f32: each query's pool in the caller's order
+    (topk_rows' output in practice; rows may be a column slice of a wider tensor), entries distinct;
+    an entry outside [0, M) — the -1 of a short list — is skipped. attrs int32 [M]: the candidates'
+    attribute words, a bit per genre. target f32 [Q, 32]: each query's genre distribution p
+    (attr_profile's). With l = calibration, the list's distribution q (the mean of its items' own,
+    items without a word left out) and q~ = (1 - alpha) * q + alpha * p, step by step the pick is the
+    unpicked entry with the largest (1 - l) * score - l * KL(p || q~ of the list with it), the lowest
+    pool position among equal values; so calibration=0 returns the pool's first k eligible entries,
+    the list for a smaller k is a prefix, and a target row of zeros gives the pool order with kl = 0.
+    Returns Calibrated(idx, score, kl, n); miscalibration turns kl and n into C_KL@c.
+    Limits: 1 <= k <= N <= CALIB_MAX_POOL (ValueError before anything is loaded)."""
+    k, calibration, alpha = int(k), _calibration(calibration), _alpha(alpha)
+    if pool_idx.dim() != 2 or pool_score.shape != pool_idx.shape:
+        raise ValueError("rerank_calibrated: pool_idx and pool_score must both be [Q, N]")
+    _serving.require_index_dtype("rerank_calibrated", "pool_idx", pool_idx)
+    if pool_score.dtype != torch.float32:
+        raise TypeError(f"rerank_calibrated: pool_score must be float32, got {pool_score.dtype}")
+    _attr_words("rerank_calibrated", attrs)
+    Q, N = pool_idx.shape
+    if not isinstance(target, torch.Tensor) or target.dtype != torch.float32:
+        raise TypeError("rerank_calibrated: target must be a float32 tensor [Q, 32]")
+    if tuple(target.shape) != (Q, CALIB_GENRES):
+        raise ValueError(f"rerank_calibrated: target is {tuple(target.shape)} for {Q} queries, not [{Q}, {CALIB_GENRES}]")
+    if k < 1 or k > N:
+        raise ValueError(f"rerank_calibrated: k={k} outside [1, N={N}]")
+    if N > CALIB_MAX_POOL:
+        raise ValueError(f"rerank_calibrated: a pool of {N} entries exceeds CALIB_MAX_POOL={CALIB_MAX_POOL}")
+    lib = _ffi.load()
+    for t in (pool_idx, pool_score, attrs, target):
+        _ffi.require_device(t, "rerank_calibrated")
+    dev = pool_idx.device
+    index_dtype = pool_idx.dtype
+    pool_idx, ld = _serving.index_list(pool_idx)
+    pool_score = pool_score.detach()
+    if pool_score.stride(1) != 1 or (Q > 1 and pool_score.stride(0) != ld):  # one leading dimension serves both
+        pool_idx, pool_score, ld = pool_idx.contiguous(), pool_score.contiguous(), N
+    out_idx = torch.empty((Q, k), dtype=torch.int32, device=dev)
+    out_score = torch.empty((Q, k), dtype=torch.float32, device=dev)
+    out_kl = torch.empty((Q, k), dtype=torch.float32, device=dev)
+    out_n = torch.empty(Q, dtype=torch.int32, device=dev)
+    if Q:
+        words = attrs.detach().contiguous()
+        if words.numel() == 0:  # the library wants an address; no entry is eligible
+            words = torch.zeros(1, dtype=torch.int32, device=dev)
+        _ffi.check(lib.lgcn_rerank_calibrated(pool_idx.data_ptr(), pool_score.data_ptr(), ld, N, Q, words.data_ptr(),
+                                              attrs.numel(), target.detach().contiguous().data_ptr(), k, calibration,
+                                              alpha, out_idx.data_ptr(), out_score.data_ptr(), out_kl.data_ptr(),
+                                              out_n.data_ptr(), _ffi.stream_of(dev)), "lgcn_rerank_calibrated")
+    return Calibrated(out_idx.to(index_dtype), out_score, out_kl, out_n)
+
+
+def topk_rows_calibrated(queries: torch.Tensor, picked: torch.Tensor, candidates: torch.Tensor, k: int,
+                         calibration: float, attrs: torch.Tensor | None = None, history=None,
+                         target: torch.Tensor | None = None, pool: int | None = None, excl=None, alpha: float = 0.01,
+                         **kw) -> Calibrated:
+    """topk_rows for a relevance pool of ``pool`` entries per query, then rerank_calibrated down to k:
+    Calibrated(idx, score, kl, n), score staying the cosine relevance.
+
+    attrs: the candidates' attribute words, int32 [M] on the device (required; the same words serve a
+    where= filter). Exactly one of history — a CSR (ptr, idx), row q being query q's, or
+    (ptr, idx, rows), profiled here by attr_profile — and target (f32 [Q, 32]) says what to
+    calibrate to. pool: default max(4 * k, 64); whatever is asked for is clamped to what exists and
+    what the re-rank kernel holds, min(M, CALIB_MAX_POOL), and a pool that ends up below k is a
+    ValueError. excl and kw (where, among, cap, subset, index_dtype) are topk_rows'; under a filter a
+    query's pool holds passing candidates only, and with among= entries of the query's row only."""
+    k, calibration, alpha = int(k), _calibration(calibration), _alpha(alpha)
+    if k < 1:
+        raise ValueError(f"recommend: k={k} outside [1, {CALIB_MAX_POOL}]")
+    if queries.dim() != 2 or candidates.dim() != 2:
+        raise ValueError("recommend: queries and candidates must be 2-D")
+    if attrs is None:
+        raise ValueError("recommend: a calibrated list needs attrs (the candidates' attribute words)")
+    M = candidates.shape[0]
+    _attr_words("recommend", attrs, M)
+    if (history is None) == (target is None):
+        raise ValueError("recommend: exactly one of history= and target= says what to calibrate to")
+    Q = torch.as_tensor(picked).numel()
+    if history is not None:
+        history = _serving.csr_arg("recommend", "history", history, Q)[:3]
+    want = max(4 * k, 64) if pool is None else int(pool)
+    limits = {"the candidate count M": M, "CALIB_MAX_POOL": CALIB_MAX_POOL}
+    name = min(limits, key=limits.get)
+    pool = min(want, limits[name])
+    if pool < k:
+        if want < k:
+            raise ValueError(f"recommend: pool={want} is below k={k}")
+        raise ValueError(f"recommend: k={k} exceeds the largest pool, {limits[name]} ({name})")
+    index_dtype = kw.pop("index_dtype", torch.int64)
+    if index_dtype not in (torch.int64, torch.int32):
+        raise ValueError(f"recommend: index_dtype must be torch.int64 or torch.int32, got {index_dtype}")
+    if kw.get("where") is not None:
+        kw["attrs"] = attrs
+    idx, score = topk_rows(queries, picked, candidates, pool, excl=excl, index_dtype=torch.int32, **kw)
+    if target is None:
+        target = attr_profile(history if history[2] is not None else (history[0], history[1], torch.arange(Q)), attrs)[0]
+    out = rerank_calibrated(idx, score, attrs, target, k, calibration, alpha)
+    return out if index_dtype == torch.int32 else out._replace(idx=out.idx.to(torch.int64))
+
+
+def miscalibration(kl: torch.Tensor, n: torch.Tensor, ks) -> torch.Tensor:
+    """C_KL@c of calibrated lists, float64 [Q, C] for the sorted distinct cutoffs of ``ks``: the KL
+    divergence between the target and the list's first c' = min(c, n) items, kl[:, c' - 1]; NaN where
+    n == 0. kl and n are Calibrated's. Plain torch on the tensors' device; CPU tensors work too."""
+    if kl.dim() != 2 or n.shape != kl.shape[:1]:
+        raise ValueError(f"miscalibration: kl {tuple(kl.shape)} / n {tuple(n.shape)} are not [Q, k] / [Q]")
+    cs = sorted({int(c) for c in ks})
+    if not cs or cs[0] < 1 or cs[-1] > kl.shape[1]:
+        raise ValueError(f"miscalibration: cutoffs {cs} outside [1, k={kl.shape[1]}]")
+    c = torch.tensor(cs, dtype=torch.int64, device=kl.device)
+    cp = torch.minimum(n.to(torch.int64).clamp(min=0)[:, None], c[None, :])
+    got = kl.to(torch.float64).gather(1, (cp - 1).clamp(min=0))
+    return torch.where(cp >= 1, got, torch.full((), float("nan"), dtype=torch.float64, device=kl.device))
 
 
 def topk_items(user_emb: torch.Tensor, item_emb: torch.Tensor, users, k: int, seen=None, among=None, **kw):

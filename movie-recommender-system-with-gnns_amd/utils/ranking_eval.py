@@ -18,7 +18,8 @@ import torch
 
 
 def evaluate_ranking(model: torch.nn.Module, train_edge_index: torch.Tensor, heldout_edge_index: torch.Tensor,
-                     device, ks=(20,), embeddings: str = "raw", diversity=None, pool=None) -> dict:
+                     device, ks=(20,), embeddings: str = "raw", diversity=None, pool=None, calibration=None,
+                     data_handler=None, attrs=None) -> dict:
     """Every user with a held-out edge gets all items ranked, the items of their training edges left
     out, and the means of recall / precision / hit_rate / ndcg / mrr at each cutoff of ``ks`` come
     back as lgcn_amd.metrics.summarize's dict ({'users': n, 'recall@20': ..., ...}).
@@ -28,11 +29,26 @@ def evaluate_ranking(model: torch.nn.Module, train_edge_index: torch.Tensor, hel
     LightGCN paper's protocol. Runs on the HIP path: the model must be on a ROCm device.
     diversity / pool: lgcn_amd.metrics.evaluate_ranking's — None evaluates the relevance lists; a
     float in [0, 1] evaluates the MMR re-ranked lists utils.recommend.recommend_for_users serves with
-    the same arguments and adds 'ild@c' (intra-list diversity) per cutoff; 0.0 only measures."""
+    the same arguments and adds 'ild@c' (intra-list diversity) per cutoff; 0.0 only measures.
+    calibration (with pool): lgcn_amd.metrics.evaluate_ranking's — a float in [0, 1] evaluates the
+    calibrated lists utils.recommend.recommend_for_users serves with the same argument, each user's
+    target being the genre mix of their training items, and adds 'ckl@c' (the KL divergence between
+    that mix and the list's) per cutoff; 0.0 only measures. The genre words come from
+    utils.recommend.genre_table(data_handler), or are given as attrs (int32 [num_items])."""
     if embeddings not in ("raw", "propagated"):
         raise ValueError(f"evaluate_ranking: embeddings must be 'raw' or 'propagated', got {embeddings!r}")
     from lgcn_amd import metrics
     from lgcn_amd.recommend import seen_csr
+
+    if calibration is None:
+        if data_handler is not None or attrs is not None:
+            raise ValueError("evaluate_ranking: data_handler / attrs give the calibration's genre words and need calibration")
+    elif attrs is None:
+        if data_handler is None:
+            raise ValueError("evaluate_ranking: calibration needs the genre words: data_handler= or attrs=")
+        from utils.recommend import genre_table
+
+        attrs = genre_table(data_handler)[1]
 
     model.eval()
     U, I = model.num_users, model.num_items
@@ -45,6 +61,9 @@ def evaluate_ranking(model: torch.nn.Module, train_edge_index: torch.Tensor, hel
                                                       item_indices=torch.arange(I, device=device))
         else:
             user_emb, item_emb = model(train_edge_index)
+        if calibration is not None:
+            return metrics.evaluate_ranking(user_emb, item_emb, truth, ks=ks, seen=seen, diversity=diversity, pool=pool,
+                                            calibration=calibration, attrs=attrs.to(device))
         return metrics.evaluate_ranking(user_emb, item_emb, truth, ks=ks, seen=seen, diversity=diversity, pool=pool)
 
 

@@ -23,6 +23,11 @@ movie (``genre_table``), tested on the device where the score is tested
 a watchlist, tonight's schedule, another model's shortlist — at the cost of the sets' sizes
 (lgcn_amd.recommend.topk_rows' among; ``python utils/recommend.py USER_ID --among 1,296,318``, likewise
 with ``--movies``).
+``calibration=`` (recommend_for_users, recommend_for_histories) serves a list that keeps the genre mix of
+the user's own history — 70 % drama and 30 % comedy watched, about that served — by a greedy re-rank of
+a relevance pool against the KL divergence between the two genre distributions, on the device
+(lgcn_amd.recommend.topk_rows_calibrated; ``python utils/recommend.py USER_ID --calibrate 0.5``, likewise
+with ``--movies``).
 ``recommend_for_groups`` / ``recommend_for_group`` serve several users ONE list — "what do the four of us
 watch tonight?" — by least misery (the minimum of the members' scores), most pleasure (the maximum) or
 the average, optionally without anything a member scores under a floor; the members' scores are reduced
@@ -160,9 +165,14 @@ def _ranked(idx: torch.Tensor, score: torch.Tensor):
     return [[(int(i), float(s)) for i, s in zip(ri.tolist(), rs.tolist()) if i >= 0] for ri, rs in zip(idx, score)]
 
 
-def _check_options(who: str, diversity, pool, explain) -> Optional[int]:
-    """The batch calls' ``pool`` / ``explain`` refusals under the caller's prefix; explain as an int, or None."""
-    if diversity is None and pool is not None:
+def _check_options(who: str, diversity, pool, explain, calibration=None) -> Optional[int]:
+    """The batch calls' ``pool`` / ``explain`` / ``calibration`` refusals under the caller's prefix; explain as
+    an int, or None."""
+    if diversity is not None and calibration is not None:
+        raise ValueError(f"{who}: diversity and calibration are two re-ranks; one per call")
+    if calibration is not None:
+        _rec._calibration(calibration)
+    if diversity is None and calibration is None and pool is not None:
         raise ValueError(f"{who}: pool is the re-rank's pool and needs diversity")
     if explain is None:
         return None
@@ -173,14 +183,21 @@ def _check_options(who: str, diversity, pool, explain) -> Optional[int]:
 
 
 def _serve(handler: Any, out: list, slots: Sequence[int], queries: torch.Tensor, item_emb: torch.Tensor, k: int, excl,
-           diversity, pool, flt: dict, explain=None) -> list:
+           diversity, pool, flt: dict, explain=None, calibration=None, profile=None) -> list:
     """The batch calls' common end: rank item_emb's rows for the queries (one row per slot of ``slots``;
-    topk_rows, or topk_rows_diverse with ``diversity``), explain the lists (``explain``: None, or a
-    function of the ranked indices that returns lgcn_amd.explain's Explained) and write each query's
+    topk_rows, topk_rows_diverse with ``diversity``, or topk_rows_calibrated with ``calibration`` towards
+    the genre mix of ``profile`` = (history CSR with a row per query, its weights or None)), explain the
+    lists (``explain``: None, or a function of the ranked indices that returns lgcn_amd.explain's Explained) and write each query's
     [{'movie_id', 'title', 'score'[, 'because']}] into ``out`` at its slot. Returns out."""
     picked = torch.arange(len(slots))
     with torch.no_grad():
-        if diversity is None:
+        if calibration is not None:
+            attrs = flt["attrs"] if "attrs" in flt else genre_table(handler)[1].to(queries.device)
+            target = _rec.attr_profile(profile[0], attrs, weights=profile[1])[0]
+            idx, score = _rec.topk_rows_calibrated(queries, picked, item_emb, k, calibration, attrs=attrs, target=target,
+                                                   pool=pool, excl=excl,
+                                                   **{key: v for key, v in flt.items() if key != "attrs"})[:2]
+        elif diversity is None:
             idx, score = _rec.topk_rows(queries, picked, item_emb, k, excl=excl, **flt)
         else:
             idx, score = _rec.topk_rows_diverse(queries, picked, item_emb, k, diversity, pool=pool, excl=excl, **flt)[:2]
@@ -254,7 +271,8 @@ def recommend_for_users(model: torch.nn.Module, user_ids: Sequence[int], data_ha
                         diversity: Optional[float] = None, pool: Optional[int] = None,
                         explain: Optional[int] = None, genres: Optional[Sequence[str]] = None,
                         genres_all: Optional[Sequence[str]] = None, without_genres: Optional[Sequence[str]] = None,
-                        among=None) -> List[Union[Dict[str, str], List[Dict[str, Any]]]]:
+                        among=None, calibration: Optional[float] = None
+                        ) -> List[Union[Dict[str, str], List[Dict[str, Any]]]]:
     """One entry per id of ``user_ids``: the user's k best movies as [{'movie_id', 'title', 'score'}],
     or {'error': 'Invalid user ID'} for an unknown id. With ``exclude_seen`` the movies a user has an
     edge to in ``train_edge_index`` (default: every edge the handler holds, ``data_handler.edge_index``)
@@ -281,8 +299,15 @@ def recommend_for_users(model: torch.nn.Module, user_ids: Sequence[int], data_ha
     from the mapping) gets []. The list is the user's full ranking restricted to the set
     (lgcn_amd.recommend.topk_rows' among, at the cost of the sets' sizes) and combines with
     ``exclude_seen``, ``diversity`` (the pool holds movies of the set only), ``explain`` and the genre
-    arguments."""
-    explain = _check_options("recommend_for_users", diversity, pool, explain)
+    arguments.
+    ``calibration`` (a float in [0, 1]; None: today's calls and dictionaries) serves
+    lgcn_amd.recommend.topk_rows_calibrated's lists: each user's ``pool`` most relevant movies re-ranked
+    down to k so that the list's genre mix follows that of the movies the user has an edge to (in the
+    edge set ``exclude_seen`` uses, whether or not it is set; genre_table's words, a movie's genres
+    sharing its weight equally), in pick order; 0.0 is the relevance list, 1.0 follows the genre mix
+    alone. 'score' stays the cosine relevance. It works beside the genre arguments, ``among`` and
+    ``explain``, and not with ``diversity`` (ValueError: one re-rank per call)."""
+    explain = _check_options("recommend_for_users", diversity, pool, explain, calibration)
     flt = _genre_filter("recommend_for_users", data_handler, genres, genres_all, without_genres)
     user_id_map, movie_id_map = data_handler.user_id_map, data_handler.movie_id_map
     num_users, num_items = len(user_id_map), len(movie_id_map)
@@ -297,7 +322,7 @@ def recommend_for_users(model: torch.nn.Module, user_ids: Sequence[int], data_ha
     flt.update(_among_csr("recommend_for_users", among, len(user_ids), [(slot, user_ids[slot]) for slot, _ in known],
                           data_handler, dev))
     excl = history = None
-    if exclude_seen or explain is not None:
+    if exclude_seen or explain is not None or calibration is not None:
         ei = data_handler.edge_index if train_edge_index is None else train_edge_index
         history = _rec.seen_csr(ei.to(dev), num_users, num_items, by="user")
         if exclude_seen:
@@ -305,7 +330,9 @@ def recommend_for_users(model: torch.nn.Module, user_ids: Sequence[int], data_ha
     with torch.no_grad():
         user_emb, item_emb = model.get_embeddings(user_indices=users, item_indices=torch.arange(num_items, device=dev))
     why = None if explain is None else (lambda idx: _explain.explain_items(item_emb, users, idx, history, r=explain))
-    return _serve(data_handler, out, [slot for slot, _ in known], user_emb, item_emb, k, excl, diversity, pool, flt, why)
+    profile = None if calibration is None else ((history[0], history[1], users), None)
+    return _serve(data_handler, out, [slot for slot, _ in known], user_emb, item_emb, k, excl, diversity, pool, flt, why,
+                  calibration, profile)
 
 
 def recommend_for_histories(model: torch.nn.Module, histories: Sequence[Sequence[int]], data_handler: Any, k: int = 10,
@@ -314,7 +341,8 @@ def recommend_for_histories(model: torch.nn.Module, histories: Sequence[Sequence
                             diversity: Optional[float] = None, pool: Optional[int] = None,
                             explain: Optional[int] = None, genres: Optional[Sequence[str]] = None,
                             genres_all: Optional[Sequence[str]] = None,
-                            without_genres: Optional[Sequence[str]] = None, among=None
+                            without_genres: Optional[Sequence[str]] = None, among=None,
+                            calibration: Optional[float] = None
                             ) -> List[Union[Dict[str, str], List[Dict[str, Any]]]]:
     """Lists for people the model never saw — someone who has just rated a few films, an anonymous
     session: one entry per history of ``histories`` (each a sequence of MovieLens movie ids), the k
@@ -334,10 +362,12 @@ def recommend_for_histories(model: torch.nn.Module, histories: Sequence[Sequence
     'because' movies come from the supplied history (lgcn_amd.explain.explain_rows). All histories are served by one fold-in and one ranking call;
     if no history has a known id the answer comes without touching the model or the GPU.
     ``among`` is recommend_for_users': one sequence of ids for every history, a sequence of id sequences
-    aligned with ``histories``, or a mapping from a history's position to its ids."""
+    aligned with ``histories``, or a mapping from a history's position to its ids.
+    ``calibration`` is recommend_for_users', the target being the genre mix of the supplied history
+    (under its ``weights``)."""
     if embeddings not in ("raw", "propagated"):
         raise ValueError(f"recommend_for_histories: embeddings must be 'raw' or 'propagated', got {embeddings!r}")
-    explain = _check_options("recommend_for_histories", diversity, pool, explain)
+    explain = _check_options("recommend_for_histories", diversity, pool, explain, calibration)
     if weights is not None and len(weights) != len(histories):
         raise ValueError(f"recommend_for_histories: {len(weights)} weight lists for {len(histories)} histories")
     flt = _genre_filter("recommend_for_histories", data_handler, genres, genres_all, without_genres)
@@ -382,7 +412,7 @@ def recommend_for_histories(model: torch.nn.Module, histories: Sequence[Sequence
         queries = _foldin.fold_in(history, table, count=degree, weights=hw).rows
     why = None if explain is None else (lambda idx: _explain.explain_rows(idx, history, item_emb, r=explain))
     return _serve(data_handler, out, slots, queries, item_emb, k, history if exclude_history else None, diversity, pool,
-                  flt, why)
+                  flt, why, calibration, None if calibration is None else (history, hw))
 
 
 def recommend_for_groups(model: torch.nn.Module, groups_of_user_ids: Sequence[Sequence[int]], data_handler: Any,
@@ -499,6 +529,8 @@ if __name__ == '__main__':
     # a given set of movies to rank, and nothing else: --among 1,296,318
     genre_kw = dict(genres=option('--genres'), genres_all=option('--genres-all'), without_genres=option('--without'),
                     among=_cli_ids(option('--among')))
+    calibrate = option('--calibrate')  # a list that keeps the history's genre mix: --calibrate 0.5
+    genre_kw['calibration'] = None if calibrate is None else float(calibrate[0])
     filtered = any(v is not None for v in genre_kw.values())
     group = _cli_ids(option('--group'))
     strategy = (option('--strategy') or ['least_misery'])[0]
@@ -524,6 +556,8 @@ if __name__ == '__main__':
     if group is not None:  # one list for several users: --group 1,5,9 [--strategy average] [--floor 0.2]
         if genre_kw.pop('among') is not None:
             sys.exit("--among is not supported with --group")
+        if genre_kw.pop('calibration') is not None:
+            sys.exit("--calibrate is not supported with --group")
         train_data, _, _ = handler.get_datasets()
         served = recommend_for_group(model, group, handler, k=TOP_N, strategy=strategy, floor=group_floor,
                                      train_edge_index=train_data.edge_index, **genre_kw)

@@ -1,5 +1,5 @@
 """What the serving probes share (recommend_probe, rank_eval_probe, rerank_probe, explain_probe,
-foldin_probe, negatives_probe): the package on sys.path, the common options, "needs a ROCm device", the clock, warm-up
+foldin_probe, negatives_probe, calibrate_probe): the package on sys.path, the common options, "needs a ROCm device", the clock, warm-up
 plus alternating arms, the timings' record fields, and the JSON line with --out. Importing it (the
 probes run as `python tools/<name>.py`, so it is found next to them) puts the package on the path."""
 import argparse
