@@ -264,6 +264,25 @@ int lgcn_slice_schedule_build(const int64_t* rowptr, const int32_t* col, int64_t
                               lgcn_item_t* items, int64_t items_cap,
                               int64_t* offsets, lgcn_split_t* splits, int64_t splits_cap, int64_t* counts,
                               void* ws, size_t ws_bytes, lgcn_stream_t stream);
+/* The same schedule with every slice's full hub chunks (dst < 0, len == chunk) dealt to the 8 XCDs
+ * by source window (added within ABI 11: new symbols only, nothing above changes). group = items
+ * per workgroup of the kernel that will run the schedule (256 / lanes per row: 32, 16, 8 at
+ * d = 32, 64, 128), 1 <= group <= 256. Per slice, with n full chunks: they are sorted by the
+ * source id at their midpoint, col[beg + len / 2], stably in the order above; group x is sorted
+ * positions [x*n/8, (x+1)*n/8); rounds = (n / 8) / group; in the slice's sequence of full chunks
+ * the j-th run of `group` chunks, j < 8 * rounds, is the next `group` chunks of group j % 8 in
+ * ascending midpoint order, and the rest follow in ascending midpoint order. Only full chunks
+ * move, and only among the positions full chunks held (they head the slice; a row item of exactly
+ * chunk edges keeps its place among them): every other item, offsets, splits, partial slots and
+ * counts are byte for byte those of lgcn_slice_schedule_build, and so is every result computed
+ * from the schedule (chunks write independent partials). Every row is scheduled (no row_mask). */
+int lgcn_slice_schedule_xcd_workspace_size(int64_t E, int64_t N, int32_t S, int32_t chunk, int32_t group,
+                                           size_t* bytes, int64_t* items_cap);
+int lgcn_slice_schedule_build_xcd(const int64_t* rowptr, const int32_t* col, int64_t N, int64_t E,
+                                  const int64_t* bounds, int32_t S, int32_t chunk, int32_t group,
+                                  lgcn_item_t* items, int64_t items_cap, int64_t* offsets, lgcn_split_t* splits,
+                                  int64_t splits_cap, int64_t* counts, void* ws, size_t ws_bytes,
+                                  lgcn_stream_t stream);
 
 /* One launch of a source-sliced schedule (the item pass only). Row items carry flags in the high
  * bits of len: 0x20000000 = the row's FIRST segment (its sum starts at 0, else it continues from

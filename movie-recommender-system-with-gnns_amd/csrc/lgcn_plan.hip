@@ -327,6 +327,142 @@ int64_t slice_items_cap(int64_t E, int64_t N, int S, int32_t chunk) {
     return segs + E / chunk + N + 1;
 }
 
+// ---- hub chunks dealt to XCDs by source window (lgcn_slice_schedule_build_xcd) ----
+// A full hub chunk (dst < 0, len == chunk) is `chunk` consecutive CSR edges of one row, i.e. one
+// window of ascending source ids. Full chunks head every slice's items, all of one length, and
+// have no order among themselves (each writes its own partial slot), so their order inside a
+// launch is free. The item pass gives workgroup j of a launch the items [j * G, (j + 1) * G), and
+// the hardware deals workgroups to the 8 XCDs round-robin (workgroup j on XCD j % 8; a speed
+// assumption only — any deal computes the same bits). Sorting a slice's full chunks by the source
+// id at their midpoint, cutting the sorted list into 8 equal groups and giving group x to the
+// workgroups with j % 8 == x makes every XCD's hub work gather from one eighth of the midpoint
+// range instead of from the whole slice, so more of it stays in that XCD's L2.
+// A riding launch (k_spmm_ride, lgcn_spmm.hip) puts rb combine workgroups first, so item-block j
+// lands on XCD (j + rb) % 8: a rotation of the XCDs — every group still has an XCD of its own.
+constexpr int kXcds = 8;
+constexpr uint64_t kHubPadKey = (uint64_t(0xFF) << 32) | 0xFFFFFFFFull;  // slice 255 > any S <= 250
+constexpr int kHubKeyBits = 40;
+
+// Where the k-th (in ascending midpoint order) of a slice's n full chunks goes in the slice's
+// sequence of full chunks. Group x = sorted positions [x*n/8, (x+1)*n/8); rounds = (n/8)/G whole
+// workgroups per group; item-block j < 8*rounds holds the next G chunks of group j % 8; what is
+// left of every group follows in ascending midpoint order. A bijection of [0, n).
+__host__ __device__ inline int64_t hub_deal_slot(int64_t k, int64_t n, int64_t G) {
+    const int64_t rounds = (n / kXcds) / G;
+    if (rounds == 0) return k;
+    int x = static_cast<int>((k * kXcds) / n);
+    if (x > kXcds - 1) x = kXcds - 1;
+    while (x > 0 && (x * n) / kXcds > k) --x;
+    while (x < kXcds - 1 && ((x + 1) * n) / kXcds <= k) ++x;
+    const int64_t lo = (x * n) / kXcds;
+    const int64_t r = k - lo;
+    const int64_t dealt = rounds * G;  // per group
+    if (r < dealt) return ((r / G) * kXcds + x) * G + r % G;
+    return kXcds * dealt + (lo - x * dealt) + (r - dealt);
+}
+
+// flag[m] = 1 for the full hub chunks among the n_real = offsets[S] sorted items, m in [0, cap];
+// flag[cap] = 0 so the exclusive sum's last entry is their total.
+__global__ void k_hub_flag(const lgcn_item_t* __restrict__ items, int64_t cap, const int64_t* __restrict__ offsets,
+                           int S, int32_t chunk, int32_t* __restrict__ flag) {
+    const int64_t n_real = offsets[S];
+    const int64_t stride = int64_t(gridDim.x) * blockDim.x;
+    for (int64_t m = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; m <= cap; m += stride) {
+        int32_t f = 0;
+        if (m < cap && m < n_real) {
+            const lgcn_item_t it = items[m];
+            f = (it.dst < 0 && it.len == chunk) ? 1 : 0;
+        }
+        flag[m] = f;
+    }
+}
+
+__global__ void k_fill_u64(uint64_t* __restrict__ p, int64_t n, uint64_t v) {
+    const int64_t stride = int64_t(gridDim.x) * blockDim.x;
+    for (int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; i < n; i += stride) p[i] = v;
+}
+
+// The q-th full chunk (q = rank[m], slice-major in the current order): pos[q] = m, its sort key
+// (slice << 32 | source id at its midpoint) and value m. skeys: the sorted item keys (slice in the
+// top 8 bits). fcap bounds q (full chunks are disjoint runs of chunk edges: at most E / chunk).
+__global__ void k_hub_keys(const lgcn_item_t* __restrict__ items, const uint32_t* __restrict__ skeys,
+                           const int32_t* __restrict__ flag, const int32_t* __restrict__ rank, int64_t cap,
+                           const int32_t* __restrict__ col, int64_t E, int64_t fcap, int32_t* __restrict__ pos,
+                           uint64_t* __restrict__ keys, int32_t* __restrict__ vals) {
+    const int64_t stride = int64_t(gridDim.x) * blockDim.x;
+    for (int64_t m = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; m < cap; m += stride) {
+        if (!flag[m]) continue;
+        const int64_t q = rank[m];
+        const lgcn_item_t it = items[m];
+        const int64_t mid = it.beg + it.len / 2;
+        if (q < 0 || q >= fcap || mid < 0 || mid >= E) continue;
+        pos[q] = static_cast<int32_t>(m);
+        keys[q] = (uint64_t(skeys[m] >> 24) << 32) | static_cast<uint32_t>(col[mid]);
+        vals[q] = static_cast<int32_t>(m);
+    }
+}
+
+// tmp[q] = the item that is q-th in (slice, midpoint) order
+__global__ void k_hub_stage(const lgcn_item_t* __restrict__ items, const uint64_t* __restrict__ skeys64,
+                            const int32_t* __restrict__ svals, int64_t fcap, int S, int64_t cap,
+                            lgcn_item_t* __restrict__ tmp) {
+    const int64_t stride = int64_t(gridDim.x) * blockDim.x;
+    for (int64_t q = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; q < fcap; q += stride) {
+        if (static_cast<int>(skeys64[q] >> 32) >= S) continue;  // padding
+        const int64_t m = svals[q];
+        if (m >= 0 && m < cap) tmp[q] = items[m];
+    }
+}
+
+// items[pos[base + slot]] = tmp[q]: the slice's full chunks re-dealt over the positions they held
+__global__ void k_hub_deal(const lgcn_item_t* __restrict__ tmp, const uint64_t* __restrict__ skeys64,
+                           const int32_t* __restrict__ rank, const int64_t* __restrict__ offsets,
+                           const int32_t* __restrict__ pos, int64_t fcap, int S, int64_t cap, int32_t G,
+                           lgcn_item_t* __restrict__ items) {
+    const int64_t stride = int64_t(gridDim.x) * blockDim.x;
+    for (int64_t q = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; q < fcap; q += stride) {
+        const int sl = static_cast<int>(skeys64[q] >> 32);
+        if (sl >= S) continue;  // padding
+        const int64_t o0 = offsets[sl], o1 = offsets[sl + 1];
+        if (o0 < 0 || o1 < o0 || o1 > cap) continue;
+        const int64_t base = rank[o0];
+        const int64_t n = rank[o1] - base;
+        const int64_t k = q - base;
+        if (k < 0 || k >= n) continue;
+        const int64_t slot = hub_deal_slot(k, n, G);
+        if (slot < 0 || slot >= n || base + slot >= fcap) continue;
+        const int64_t m = pos[base + slot];
+        if (m >= 0 && m < cap) items[m] = tmp[q];
+    }
+}
+
+int64_t hub_chunks_cap(int64_t E, int32_t chunk) { return E / chunk + 1; }
+
+// cub temp storage of the sliced build; G > 0 adds the hub deal's scan and 64-bit sort
+size_t slice_cub_bytes(int64_t N, int64_t cap, int64_t fcap, int32_t G) {
+    size_t a = 0, b = 0, c = 0;
+    (void)hipcub::DeviceScan::ExclusiveSum(nullptr, a, (const int64_t*)nullptr, (int64_t*)nullptr,
+                                           static_cast<int>(N > 0 ? N : 1));
+    (void)hipcub::DeviceScan::ExclusiveSum(nullptr, b, (const int32_t*)nullptr, (int32_t*)nullptr,
+                                           static_cast<int>(N > 0 ? N : 1));
+    (void)hipcub::DeviceRadixSort::SortPairs(nullptr, c, (const uint32_t*)nullptr, (uint32_t*)nullptr,
+                                             (const int32_t*)nullptr, (int32_t*)nullptr, static_cast<int>(cap), 0,
+                                             32);
+    size_t m = a > b ? a : b;
+    m = m > c ? m : c;
+    if (G > 0) {
+        size_t e = 0, f = 0;
+        (void)hipcub::DeviceScan::ExclusiveSum(nullptr, e, (const int32_t*)nullptr, (int32_t*)nullptr,
+                                               static_cast<int>(cap + 1));
+        (void)hipcub::DeviceRadixSort::SortPairs(nullptr, f, (const uint64_t*)nullptr, (uint64_t*)nullptr,
+                                                 (const int32_t*)nullptr, (int32_t*)nullptr,
+                                                 static_cast<int>(fcap), 0, kHubKeyBits);
+        m = m > e ? m : e;
+        m = m > f ? m : f;
+    }
+    return m;
+}
+
 // ---- to_undirected / coalesce (reference data/dataset_handler.py:141, PyG 2.4.0) ----
 __global__ void k_pair_keys(const int64_t* __restrict__ src, const int64_t* __restrict__ dst, int64_t P, int64_t N,
                             unsigned long long* __restrict__ keys, int32_t* __restrict__ bad) {
@@ -789,22 +925,15 @@ int lgcn_schedule_build(const int64_t* rowptr, int64_t N, int64_t E, int32_t chu
 }
 
 
-int lgcn_slice_schedule_workspace_size(int64_t E, int64_t N, int32_t S, int32_t chunk, size_t* bytes,
-                                       int64_t* items_cap) {
-    if (!bytes || E < 0 || N < 0 || S < 1 || S > 250 || chunk < 1)
-        return fail(LGCN_E_ARG, "lgcn_slice_schedule_workspace_size: bad args");
+// The sliced build behind both entry points. G = 0: the (slice, longest first) order as sorted;
+// G > 0: each slice's full hub chunks re-dealt for workgroups of G items (hub_deal_slot).
+static int slice_ws_impl(const char* fn, int64_t E, int64_t N, int32_t S, int32_t chunk, int32_t G, size_t* bytes,
+                         int64_t* items_cap) {
+    if (!bytes || E < 0 || N < 0 || S < 1 || S > 250 || chunk < 1 || G < 0 || G > kBlock)
+        return fail(LGCN_E_ARG, "%s: bad args", fn);
     const int64_t cap = slice_items_cap(E, N, S, chunk);
+    const int64_t fcap = hub_chunks_cap(E, chunk);
     if (items_cap) *items_cap = cap;
-    size_t a = 0, b = 0, c = 0;
-    (void)hipcub::DeviceScan::ExclusiveSum(nullptr, a, (const int64_t*)nullptr, (int64_t*)nullptr,
-                                           static_cast<int>(N > 0 ? N : 1));
-    (void)hipcub::DeviceScan::ExclusiveSum(nullptr, b, (const int32_t*)nullptr, (int32_t*)nullptr,
-                                           static_cast<int>(N > 0 ? N : 1));
-    (void)hipcub::DeviceRadixSort::SortPairs(nullptr, c, (const uint32_t*)nullptr, (uint32_t*)nullptr,
-                                             (const int32_t*)nullptr, (int32_t*)nullptr, static_cast<int>(cap), 0,
-                                             32);
-    size_t m = a > b ? a : b;
-    m = m > c ? m : c;
     Carver cv{nullptr, 0};
     cv.take<int64_t>(N);
     cv.take<int64_t>(N);
@@ -817,24 +946,33 @@ int lgcn_slice_schedule_workspace_size(int64_t E, int64_t N, int32_t S, int32_t 
     cv.take<uint32_t>(cap);
     cv.take<int32_t>(cap);
     cv.take<int32_t>(cap);
-    cv.take<char>(m);
+    cv.take<char>(slice_cub_bytes(N, cap, fcap, G));
+    if (G > 0) {
+        cv.take<int32_t>(cap + 1);  // flag
+        cv.take<int32_t>(cap + 1);  // rank
+        cv.take<int32_t>(fcap);     // pos
+        cv.take<uint64_t>(fcap);    // keys in
+        cv.take<uint64_t>(fcap);    // keys out
+        cv.take<int32_t>(fcap);     // vals in
+        cv.take<int32_t>(fcap);     // vals out
+    }
     *bytes = cv.used + 256;
     return LGCN_OK;
 }
 
-int lgcn_slice_schedule_build(const int64_t* rowptr, const int32_t* col, int64_t N, int64_t E,
-                              const int64_t* bounds, int32_t S, int32_t chunk, const uint8_t* row_mask,
-                              lgcn_item_t* items, int64_t items_cap,
-                              int64_t* offsets, lgcn_split_t* splits, int64_t splits_cap, int64_t* counts,
-                              void* ws, size_t ws_bytes, lgcn_stream_t stream) {
+static int slice_build_impl(const char* fn, const int64_t* rowptr, const int32_t* col, int64_t N, int64_t E,
+                            const int64_t* bounds, int32_t S, int32_t chunk, int32_t G, const uint8_t* row_mask,
+                            lgcn_item_t* items, int64_t items_cap, int64_t* offsets, lgcn_split_t* splits,
+                            int64_t splits_cap, int64_t* counts, void* ws, size_t ws_bytes, lgcn_stream_t stream) {
     if (!rowptr || !bounds || !counts || !offsets || N <= 0 || E < 0 || S < 1 || S > 250 || chunk < 1 ||
-        chunk >= (1 << 24) || (E > 0 && !col))
-        return fail(LGCN_E_ARG, "lgcn_slice_schedule_build: bad args");
+        chunk >= (1 << 24) || (E > 0 && !col) || G < 0 || G > kBlock)
+        return fail(LGCN_E_ARG, "%s: bad args", fn);
     if (N > INT32_MAX || E > INT32_MAX) return fail(LGCN_E_UNSUPPORTED, "slice schedule: sizes exceed int32");
     hipStream_t s = as_stream(stream);
     const int64_t cap = slice_items_cap(E, N, S, chunk);
+    const int64_t fcap = hub_chunks_cap(E, chunk);
     if (!items || items_cap < cap || !splits || splits_cap < N)
-        return fail(LGCN_E_ARG, "lgcn_slice_schedule_build: items_cap %lld < %lld or splits_cap %lld < %lld",
+        return fail(LGCN_E_ARG, "%s: items_cap %lld < %lld or splits_cap %lld < %lld", fn,
                     (long long)items_cap, (long long)cap, (long long)splits_cap, (long long)N);
     Carver c{static_cast<char*>(ws), ws_bytes};
     int64_t* n_items = c.take<int64_t>(N);
@@ -848,15 +986,20 @@ int lgcn_slice_schedule_build(const int64_t* rowptr, const int32_t* col, int64_t
     uint32_t* k_out = c.take<uint32_t>(cap);
     int32_t* i_in = c.take<int32_t>(cap);
     int32_t* i_out = c.take<int32_t>(cap);
-    size_t a = 0, b = 0, cb = 0;
-    (void)hipcub::DeviceScan::ExclusiveSum(nullptr, a, (const int64_t*)nullptr, (int64_t*)nullptr, static_cast<int>(N));
-    (void)hipcub::DeviceScan::ExclusiveSum(nullptr, b, (const int32_t*)nullptr, (int32_t*)nullptr, static_cast<int>(N));
-    (void)hipcub::DeviceRadixSort::SortPairs(nullptr, cb, (const uint32_t*)nullptr, (uint32_t*)nullptr,
-                                             (const int32_t*)nullptr, (int32_t*)nullptr, static_cast<int>(cap), 0, 32);
-    size_t cub_bytes = a > b ? a : b;
-    cub_bytes = cub_bytes > cb ? cub_bytes : cb;
+    size_t cub_bytes = slice_cub_bytes(N, cap, fcap, G);
     void* cub_tmp = c.take<char>(cub_bytes);
-    if (!c.ok) return fail(LGCN_E_WORKSPACE, "lgcn_slice_schedule_build: workspace %zu < %zu", ws_bytes, c.used);
+    int32_t *h_flag = nullptr, *h_rank = nullptr, *h_pos = nullptr, *h_vin = nullptr, *h_vout = nullptr;
+    uint64_t *h_kin = nullptr, *h_kout = nullptr;
+    if (G > 0) {
+        h_flag = c.take<int32_t>(cap + 1);
+        h_rank = c.take<int32_t>(cap + 1);
+        h_pos = c.take<int32_t>(fcap);
+        h_kin = c.take<uint64_t>(fcap);
+        h_kout = c.take<uint64_t>(fcap);
+        h_vin = c.take<int32_t>(fcap);
+        h_vout = c.take<int32_t>(fcap);
+    }
+    if (!c.ok) return fail(LGCN_E_WORKSPACE, "%s: workspace %zu < %zu", fn, ws_bytes, c.used);
     // counts[3] = 1 if some row's neighbours are not ascending (the caller falls back)
     if (int rc = check_hip(hipMemsetAsync(counts, 0, 4 * sizeof(int64_t), s), "memset counts")) return rc;
     const unsigned g = grid_for(N, kBlock, 8192);
@@ -887,7 +1030,67 @@ int lgcn_slice_schedule_build(const int64_t* rowptr, const int32_t* col, int64_t
     if (int rc = check_launch("k_sched_gather")) return rc;
     // offsets over the sorted keys; padding keys (0xFFFFFFFF) sort after every real slice
     k_slice_offsets<<<1, 256, 0, s>>>(k_out, cap, S, offsets);
-    return check_launch("k_slice_offsets");
+    if (int rc = check_launch("k_slice_offsets")) return rc;
+    if (G == 0 || E == 0) return LGCN_OK;
+
+    // the hub deal: permute each slice's full chunks among the positions they hold. Rows with an
+    // unsorted neighbour list (counts[3]) make midpoints meaningless but nothing unsafe: every
+    // index below is bounded, and the caller discards that schedule.
+    k_hub_flag<<<grid_for(cap + 1, kBlock, 8192), kBlock, 0, s>>>(items, cap, offsets, S, chunk, h_flag);
+    if (int rc = check_launch("k_hub_flag")) return rc;
+    t = cub_bytes;
+    if (int rc = check_hip(hipcub::DeviceScan::ExclusiveSum(cub_tmp, t, h_flag, h_rank, static_cast<int>(cap + 1), s), "scan hub chunks")) return rc;
+    k_fill_u64<<<grid_for(fcap, kBlock, 8192), kBlock, 0, s>>>(h_kin, fcap, kHubPadKey);
+    if (int rc = check_launch("k_fill_u64")) return rc;
+    k_fill_u32<<<grid_for(fcap, kBlock, 8192), kBlock, 0, s>>>(reinterpret_cast<uint32_t*>(h_vin), fcap, 0u);
+    if (int rc = check_launch("k_fill_u32")) return rc;
+    k_fill_u32<<<grid_for(fcap, kBlock, 8192), kBlock, 0, s>>>(reinterpret_cast<uint32_t*>(h_pos), fcap, 0u);
+    if (int rc = check_launch("k_fill_u32")) return rc;
+    k_hub_keys<<<grid_for(cap, kBlock, 8192), kBlock, 0, s>>>(items, k_out, h_flag, h_rank, cap, col, E, fcap, h_pos,
+                                                             h_kin, h_vin);
+    if (int rc = check_launch("k_hub_keys")) return rc;
+    t = cub_bytes;
+    // LSD radix sort is stable: chunks of equal midpoint keep their current (row, CSR) order
+    if (int rc = check_hip(hipcub::DeviceRadixSort::SortPairs(cub_tmp, t, h_kin, h_kout, h_vin, h_vout,
+                                                              static_cast<int>(fcap), 0, kHubKeyBits, s),
+                           "SortPairs(hub chunks)"))
+        return rc;
+    // raw is free after the gather and holds cap >= fcap items: the staging copy
+    k_hub_stage<<<grid_for(fcap, kBlock, 8192), kBlock, 0, s>>>(items, h_kout, h_vout, fcap, S, cap, raw);
+    if (int rc = check_launch("k_hub_stage")) return rc;
+    k_hub_deal<<<grid_for(fcap, kBlock, 8192), kBlock, 0, s>>>(raw, h_kout, h_rank, offsets, h_pos, fcap, S, cap, G,
+                                                              items);
+    return check_launch("k_hub_deal");
+}
+
+int lgcn_slice_schedule_workspace_size(int64_t E, int64_t N, int32_t S, int32_t chunk, size_t* bytes,
+                                       int64_t* items_cap) {
+    return slice_ws_impl("lgcn_slice_schedule_workspace_size", E, N, S, chunk, 0, bytes, items_cap);
+}
+
+int lgcn_slice_schedule_build(const int64_t* rowptr, const int32_t* col, int64_t N, int64_t E,
+                              const int64_t* bounds, int32_t S, int32_t chunk, const uint8_t* row_mask,
+                              lgcn_item_t* items, int64_t items_cap,
+                              int64_t* offsets, lgcn_split_t* splits, int64_t splits_cap, int64_t* counts,
+                              void* ws, size_t ws_bytes, lgcn_stream_t stream) {
+    return slice_build_impl("lgcn_slice_schedule_build", rowptr, col, N, E, bounds, S, chunk, 0, row_mask, items,
+                            items_cap, offsets, splits, splits_cap, counts, ws, ws_bytes, stream);
+}
+
+int lgcn_slice_schedule_xcd_workspace_size(int64_t E, int64_t N, int32_t S, int32_t chunk, int32_t group,
+                                           size_t* bytes, int64_t* items_cap) {
+    if (group < 1) return fail(LGCN_E_ARG, "lgcn_slice_schedule_xcd_workspace_size: group %d < 1", group);
+    return slice_ws_impl("lgcn_slice_schedule_xcd_workspace_size", E, N, S, chunk, group, bytes, items_cap);
+}
+
+int lgcn_slice_schedule_build_xcd(const int64_t* rowptr, const int32_t* col, int64_t N, int64_t E,
+                                  const int64_t* bounds, int32_t S, int32_t chunk, int32_t group,
+                                  lgcn_item_t* items, int64_t items_cap, int64_t* offsets, lgcn_split_t* splits,
+                                  int64_t splits_cap, int64_t* counts, void* ws, size_t ws_bytes,
+                                  lgcn_stream_t stream) {
+    if (group < 1) return fail(LGCN_E_ARG, "lgcn_slice_schedule_build_xcd: group %d < 1", group);
+    return slice_build_impl("lgcn_slice_schedule_build_xcd", rowptr, col, N, E, bounds, S, chunk, group, nullptr,
+                            items, items_cap, offsets, splits, splits_cap, counts, ws, ws_bytes, stream);
 }
 
 

@@ -295,7 +295,8 @@ class PropagationPlan:
 
             forced = tuning.get().slice_mb is not None
             if forced or self.num_edges >= 8 * (len(bounds) - 1) * self.num_nodes:
-                out = build_sliced(direction, self.num_nodes, bounds, sliced_chunk(direction.chunk)) or direction
+                out = build_sliced(direction, self.num_nodes, bounds, sliced_chunk(direction.chunk),
+                                   d=d) or direction
         self._sched[key] = out
         return out
 

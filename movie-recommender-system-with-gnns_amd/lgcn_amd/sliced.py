@@ -9,7 +9,9 @@ Rows with a segment longer than ``chunk`` (hubs) are cut into chunks whose parti
 pass adds after the last slice (as the default schedule does for its split rows).
 
 Built on the device from a direction's CSR by lgcn_slice_schedule_build (csrc/lgcn_plan.hip),
-once per (edge set, width).
+once per (edge set, width). With the width known (and lgcn_amd.tuning's slice_hub_xcd on) the
+builder is lgcn_slice_schedule_build_xcd: the same schedule with each slice's full hub chunks dealt
+to the XCDs by source window (a permutation of items that have no order among themselves).
 """
 from __future__ import annotations
 
@@ -69,32 +71,58 @@ def slice_bounds(N: int, U: int, d: int, slice_bytes: int) -> list[int]:
     return sorted(set(out))
 
 
+def items_per_workgroup(d: int) -> int:
+    """Items one workgroup of the item pass sums at width d (csrc/lgcn_spmm.hip dispatch: 256
+    threads, d / 4 lanes per row up to a wave; any other width one wave per item)."""
+    if d in (4, 8, 16, 32, 64, 128, 256, 512, 1024):
+        return 256 // min(64, d // 4)
+    return 4
+
+
 def build_sliced(f: CsrDirection, N: int, bounds: list[int], chunk: int = 256,
-                 row_mask: torch.Tensor | None = None) -> SlicedDirection | None:
+                 row_mask: torch.Tensor | None = None, d: int | None = None) -> SlicedDirection | None:
     """The sliced schedule of direction f (lgcn_slice_schedule_build, on the device). None when
     some row's neighbours are not in ascending order (an uncoalesced edge_index): its slice
     segments would not be successive runs of its edge list, so the chain could not follow CSR
-    order — the plain schedule is used then. row_mask (uint8[N]): schedule only those rows."""
+    order — the plain schedule is used then. row_mask (uint8[N]): schedule only those rows.
+    d: the width the schedule will run at; given (and no row_mask, and tuning.slice_hub_xcd on),
+    every slice's full hub chunks are dealt to the XCDs by source window for that width's
+    workgroups (lgcn_slice_schedule_build_xcd): the same items in another order, the same bits."""
     import ctypes
 
+    from . import tuning
+
     lib = _ffi.load()
+    group = items_per_workgroup(int(d)) if d is not None and row_mask is None and tuning.get().slice_hub_xcd else 0
     dev = f.rowptr.device
     E = f.col.numel()
     S = len(bounds) - 1
     stream = _ffi.stream_of(dev)
     nbytes, cap = _ffi._sz(0), ctypes.c_int64(0)
-    _ffi.check(lib.lgcn_slice_schedule_workspace_size(E, N, S, chunk, ctypes.byref(nbytes), ctypes.byref(cap)),
-               "lgcn_slice_schedule_workspace_size")
+    if group:
+        _ffi.check(lib.lgcn_slice_schedule_xcd_workspace_size(E, N, S, chunk, group, ctypes.byref(nbytes),
+                                                              ctypes.byref(cap)),
+                   "lgcn_slice_schedule_xcd_workspace_size")
+    else:
+        _ffi.check(lib.lgcn_slice_schedule_workspace_size(E, N, S, chunk, ctypes.byref(nbytes), ctypes.byref(cap)),
+                   "lgcn_slice_schedule_workspace_size")
     ws = torch.empty(max(1, nbytes.value), dtype=torch.uint8, device=dev)
     items = torch.empty((cap.value, 2), dtype=torch.int64, device=dev)
     splits = torch.empty((max(N, 1), 4), dtype=torch.int32, device=dev)
     offsets = torch.empty(S + 1, dtype=torch.int64, device=dev)
     counts = torch.zeros(4, dtype=torch.int64, device=dev)
     bnd = torch.tensor(bounds, dtype=torch.int64, device=dev)
-    _ffi.check(lib.lgcn_slice_schedule_build(f.rowptr.data_ptr(), _ffi.ptr(f.col), N, E, bnd.data_ptr(), S, chunk,
-                                             _ffi.ptr(row_mask), items.data_ptr(), cap.value, offsets.data_ptr(), splits.data_ptr(),
-                                             splits.shape[0], counts.data_ptr(), ws.data_ptr(), ws.numel(), stream),
-               "lgcn_slice_schedule_build")
+    if group:
+        _ffi.check(lib.lgcn_slice_schedule_build_xcd(f.rowptr.data_ptr(), _ffi.ptr(f.col), N, E, bnd.data_ptr(), S,
+                                                     chunk, group, items.data_ptr(), cap.value, offsets.data_ptr(),
+                                                     splits.data_ptr(), splits.shape[0], counts.data_ptr(),
+                                                     ws.data_ptr(), ws.numel(), stream),
+                   "lgcn_slice_schedule_build_xcd")
+    else:
+        _ffi.check(lib.lgcn_slice_schedule_build(f.rowptr.data_ptr(), _ffi.ptr(f.col), N, E, bnd.data_ptr(), S, chunk,
+                                                 _ffi.ptr(row_mask), items.data_ptr(), cap.value, offsets.data_ptr(), splits.data_ptr(),
+                                                 splits.shape[0], counts.data_ptr(), ws.data_ptr(), ws.numel(), stream),
+                   "lgcn_slice_schedule_build")
     host = torch.cat([counts, offsets]).cpu().tolist()  # one read-back per plan
     n_items, n_splits, n_partials, unsorted = host[:4]
     off = host[4:]

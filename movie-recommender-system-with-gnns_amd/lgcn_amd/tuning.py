@@ -35,6 +35,10 @@ class Tuning:
     slice_mb: float | None = None
     # K-layer sliced forward with the split-row combines riding in the next slice group's launch
     slice_ride: bool = True
+    # sliced schedules: each slice's full hub chunks dealt to the XCDs by source window
+    # (lgcn_slice_schedule_build_xcd; read by lgcn_amd.sliced.build_sliced when a schedule is
+    # built). False: lgcn_slice_schedule_build's order. The same bits either way
+    slice_hub_xcd: bool = True
     # large-batch negatives grouping: "count" (lgcn_group_keys) or "radix" (lgcn_csr_build)
     neg_grouping: str = "count"
     # batch size from which the negatives take the sorted scatter instead of the range scatter
