@@ -5,6 +5,10 @@ instead of ~20 PyTorch multi-tensor launches, with no host synchronisation.
 Same hyper-parameters and update rule as torch.optim.Adam's defaults (betas (0.9, 0.999),
 eps 1e-8, no weight decay, no amsgrad); bias corrections are computed in double on the host
 from a Python step counter, as torch does when not capturable.
+
+A launch takes at most 8 tensors. With more parameters the step runs in chunks of 8, and the clip
+coefficient still comes from the norm over all of them (FusedAdam._group_norm), as
+clip_grad_norm_(model.parameters()) has it.
 """
 from __future__ import annotations
 
@@ -29,6 +33,8 @@ class FusedAdam(torch.optim.Optimizer):
         self.last_norm = None  # device tensor [total_norm, clip_coef] of the last clipped step
         self._norm_ws = None
         self._norm_out = None
+        self._group_ws = None   # more than 8 parameters: one norm workspace per chunk of 8
+        self._group_out = None
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -37,6 +43,7 @@ class FusedAdam(torch.optim.Optimizer):
             with torch.enable_grad():
                 loss = closure()
         lib = _ffi.load()
+        work = []  # (group, its parameters with a gradient in chunks of 8)
         for group in self.param_groups:
             ps = [p for p in group["params"] if p.grad is not None]
             if not ps:
@@ -54,20 +61,54 @@ class FusedAdam(torch.optim.Optimizer):
             if self.capturable and "dev_step" not in group:
                 group["dev_step"] = torch.zeros(1, dtype=torch.float64, device=ps[0].device)
                 group["dev_scalars"] = torch.zeros(2, dtype=torch.float32, device=ps[0].device)
-            for i in range(0, len(ps), 8):
-                self._step_chunk(lib, group, ps[i:i + 8], first=(i == 0))
+            work.append((group, [ps[i:i + 8] for i in range(0, len(ps), 8)]))
+        # clip_grad_norm_ takes the norm over every parameter with a gradient: with more than one
+        # chunk, the coefficient of all of them together, before any of them steps (one chunk:
+        # _step_chunk's own lgcn_grad_norm is that norm)
+        every = [c for _, chunks in work for c in chunks]
+        clip = self._group_norm(lib, every) if self.fused_clip_norm is not None and len(every) > 1 else None
+        for group, chunks in work:
+            for i, chunk in enumerate(chunks):
+                self._step_chunk(lib, group, chunk, first=(i == 0), clip=clip)
         return loss
 
-    def _step_chunk(self, lib, group, ps, first=True):
-        dev = ps[0].device
-        stream = _ffi.stream_of(dev)
+    def _tensors(self, ps):
         arr = (_ffi.AdamTensor * len(ps))()
         for k, p in enumerate(ps):
             st = self.state[p]
             arr[k] = _ffi.AdamTensor(p.data_ptr(), p.grad.data_ptr(), st["exp_avg"].data_ptr(),
                                      st["exp_avg_sq"].data_ptr(), p.numel())
+        return arr
+
+    def _group_norm(self, lib, chunks):
+        """[total_norm, clip_coef] over every chunk's gradients (clip_grad_norm_ over all the
+        parameters), on the device: lgcn_grad_norm leaves each chunk's block partials of the sum of
+        squares in the chunk's own workspace (cleared first: a short chunk fills only a part of
+        it), and lgcn_row_grad_norm_finish sums all of them in a fixed order."""
+        dev = chunks[0][0].device
+        stream = _ffi.stream_of(dev)
+        per = lib.lgcn_grad_norm_workspace_floats()
+        if self._group_ws is None or self._group_ws.device != dev or self._group_ws.shape[0] != len(chunks):
+            self._group_ws = torch.empty((len(chunks), per), dtype=torch.float32, device=dev)
+            self._group_out = torch.empty((len(chunks) + 1, 2), dtype=torch.float32, device=dev)
+        ws, out = self._group_ws, self._group_out
+        ws.zero_()
+        for i, ps in enumerate(chunks):
+            _ffi.check(lib.lgcn_grad_norm(self._tensors(ps), len(ps), float(self.fused_clip_norm), ws[i].data_ptr(),
+                                          out[i + 1].data_ptr(), stream), "lgcn_grad_norm")
+        _ffi.check(lib.lgcn_row_grad_norm_finish(ws.data_ptr(), ws.numel(), float(self.fused_clip_norm),
+                                                 out[0].data_ptr(), None, stream), "lgcn_row_grad_norm_finish")
+        self.last_norm = out[0]
+        return out[0]
+
+    def _step_chunk(self, lib, group, ps, first=True, clip=None):
+        dev = ps[0].device
+        stream = _ffi.stream_of(dev)
+        arr = self._tensors(ps)
         clip_ptr = None
-        if self.fused_clip_norm is not None:
+        if clip is not None:
+            clip_ptr = clip.data_ptr()
+        elif self.fused_clip_norm is not None:
             if self._norm_ws is None or self._norm_ws.device != dev:
                 self._norm_ws = torch.empty(lib.lgcn_grad_norm_workspace_floats(), dtype=torch.float32, device=dev)
                 self._norm_out = torch.empty(2, dtype=torch.float32, device=dev)
