@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 import torch
 
+import owner_checker
 from conftest import ROOT
 
 pytestmark = pytest.mark.gpu
@@ -36,10 +37,11 @@ def _pack(lib, g, U, d, rows_a, keys_b, first_b, skip_b, cap, gpu):
 
 
 @pytest.mark.parametrize("records", [False, True])
-@pytest.mark.parametrize("d", [64, 128])
+@pytest.mark.parametrize("d", owner_checker.WIDTHS)
 def test_exchange_kernels_match_sequential_restatement(gpu, d, records):
     """pack (3 ranks' lists with duplicates, filters, padding) -> mark_first -> accumulate(/3),
-    bitwise against: for each slot in rank order, first occurrence stores, later ones add, /3.
+    bitwise against: for each slot in rank order, first occurrence stores, later ones add, /3
+    (owner_checker.rank_ordered_mean), at every supported width.
     records: the rows read from RowExchange's one-collective layout (rank blocks of
     [ids as 2*cap words | rows], rank_stride = cap*(d+2)) instead of one dense row table."""
     from lgcn_amd import _ffi
@@ -87,24 +89,12 @@ def test_exchange_kernels_match_sequential_restatement(gpu, d, records):
         rows_ptr, stride = rows_all.data_ptr(), cap * d
     _ffi.check(lib.lgcn_rows_accumulate(ids_all.data_ptr(), rows_ptr, W, cap, stride, first.data_ptr(),
                                         g[:U].data_ptr(), g[U:].data_ptr(), U, d, float(W), s), "acc")
-    ids_h = ids_all.cpu().numpy()
-    rows_h = rows_all.cpu()
-    ref = {}
-    seen = set()
-    first_ref = np.zeros(W * cap, np.uint8)
-    for i, r in enumerate(ids_h):
-        if r < 0:
-            continue
-        if r not in seen:
-            seen.add(r)
-            first_ref[i] = 1
-            ref[r] = rows_h[i].clone()
-        else:
-            ref[r] = ref[r] + rows_h[i]
+    first_ref, ref = owner_checker.rank_ordered_mean(ids_all.cpu().numpy(), rows_all.cpu().numpy(), W, cap, float(W))
+    seen = set(ref)
     assert np.array_equal(first.cpu().numpy(), first_ref)
     gh = g.cpu()
     for r, v in ref.items():
-        assert torch.equal(gh[r], v / W), r
+        assert torch.equal(gh[r], torch.from_numpy(v)), r
     outside = np.setdiff1d(np.arange(N), np.array(sorted(seen)))
     assert torch.isnan(gh[outside]).all()
 
