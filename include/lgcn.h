@@ -1062,6 +1062,36 @@ int lgcn_score_filter_groups(const float* Qn, int64_t Gpad, int64_t Gvalid, int3
                              const uint32_t* thr, uint32_t* list_key, int32_t* list_idx, int32_t* list_n, int32_t cap,
                              lgcn_stream_t stream);
 
+/* Per-candidate score boosts (added under ABI 11, purely additive): "show less of what everybody has
+ * seen", "lift this month's releases", "bury a title without removing it", the item bias of a second
+ * model. A candidate carries one f32 boost[j], indexed by candidate index as the attribute words are
+ * (by r * stride in lgcn_score_filter_boost), one vector per call, shared by all queries.
+ *   The key of pair (q, j) is the filter's key of  s + boost[j]:  s the score lgcn_score_filter's f32
+ *   MFMA chain gives the pair, bit for bit, and the sum ONE IEEE f32 addition (round to nearest even,
+ *   nothing fused: the library is built with -ffp-contract=off).
+ *   Everything else is the unboosted entry points' contract, on those keys: the thresholds, the order
+ *   (key descending, index ascending, NaN first), the exclusion rows, attr / where, the -1 / -inf
+ *   padding; the score lgcn_select_topk_ranked[_attr] returns is the value of the key, the BOOSTED score.
+ *   Special values follow from the formula (nothing is checked, nothing is read on the host):
+ *     -0.0   the exact identity (s + -0.0 == s for every s, -0 and NaN included): the unboosted result;
+ *     -inf   the candidate ranks last among the eligible and still fills a slot when fewer than k others
+ *            exist (its key is -inf's; a score of +inf makes the sum a NaN);
+ *     +inf   ranks above every finite key;   NaN: ranks first.
+ * lgcn_score_filter_boost: lgcn_score_filter (attr and where NULL) or lgcn_score_filter_attr (both set)
+ *   on boosted keys. Dense mode (thr NULL) only without a filter, as before: the ranked selection applies
+ *   the predicate to dense rows. LGCN_E_ARG, before any device work: boost NULL, attr without where or
+ *   where without attr, thr NULL with attr set, and the unboosted entry points' own refusals.
+ * lgcn_score_lists_boost: lgcn_score_lists on boosted keys (both launches); boost NULL is LGCN_E_ARG.
+ * The selection kernels are the unboosted ones: they read keys. (csrc/lgcn_recall_boost.hip) */
+int lgcn_score_filter_boost(const float* Qn, int64_t Qpad, int64_t Qvalid, const float* Cn, int64_t M, int64_t stride,
+                            int32_t D, const uint32_t* thr, uint32_t* list_key, int32_t* list_idx, int32_t* list_n,
+                            int32_t cap, const uint32_t* attr, const uint32_t* where, const float* boost,
+                            lgcn_stream_t stream);
+int lgcn_score_lists_boost(const float* Qn, int64_t Qvalid, const float* Cn, int64_t M, int32_t D,
+                           const int64_t* among_ptr, const int32_t* among_idx, const int64_t* among_row,
+                           int64_t among_rows, uint32_t* list_key, int32_t* list_idx, int32_t* list_n, int32_t cap,
+                           const float* boost, lgcn_stream_t stream);
+
 /* Host-only (no GPU): `draws` consecutive numpy legacy np.random.choice(n, size, replace=False)
  * calls (reference utils/train_test.py:187) on the MT19937 state (key[624], *pos) of
  * np.random.get_state(), written to out[draws*size]; key/pos are advanced exactly as numpy would

@@ -1,7 +1,9 @@
 // The list kernels of top-k serving and Recall@k, with their launches: k_score_filter (the score tile
 // of lgcn_scoretile.h plus the filtering epilogue) and k_select_ranked (the ranked selection with an
-// exclusion row), each with the attribute filter of include/lgcn.h as a bool template parameter.
-// lgcn_recall.hip instantiates the unfiltered kernels and lgcn_recall_attr.hip the filtered ones: two
+// exclusion row), each with the attribute filter of include/lgcn.h as a bool template parameter, and
+// k_score_filter with the per-candidate boost as another.
+// lgcn_recall.hip instantiates the unfiltered kernels, lgcn_recall_attr.hip the filtered ones and
+// lgcn_recall_boost.hip the boosted filters: separate
 // translation units, so that adding a filtered instantiation leaves the unfiltered kernels' module,
 // and with it their code and register budget, exactly as it was (within one module the compiler's
 // output for one instantiation moves with the presence of the other).
@@ -45,11 +47,18 @@ __device__ __forceinline__ bool attr_passes(uint32_t a, uint32_t any, uint32_t a
 // block ahead; the masks of the wave's 32 queries sit in LDS (96 words per wave, staged once) and are
 // read per query row, only for the rows whose threshold some lane met: the lanes of a half read one
 // address, a broadcast.
-template <int D, bool kAttr = false>
+// kBoost (lgcn_score_filter_boost; dense and list mode, with kAttr or without): the score of the lane's
+// candidate j is acc[r] + boost[j * stride], one f32 addition, wherever a score is used — the threshold
+// test and the key — so the thresholds, the lists and the selection all see boosted keys. The lane's
+// boost of a block is loaded with the block's rows, one block ahead, as the attribute word is (0 past
+// M, where nothing is taken): two registers. Padding queries take nothing under any boost (the row
+// test beside the threshold test). The boosted instantiations live in lgcn_recall_boost.hip,
+// for the reason the head of this file gives for lgcn_recall_attr.hip.
+template <int D, bool kAttr = false, bool kBoost = false>
 __global__ __launch_bounds__(kBlock, ScoreTile<D>::kWaves) void k_score_filter(
     const float* __restrict__ Qn, int64_t Qvalid, int32_t nqg, int32_t nchunk, const float* __restrict__ Cn, int64_t M,
     int64_t stride, const uint32_t* __restrict__ thr, uint32_t* __restrict__ list_key, int32_t* __restrict__ list_idx,
-    int32_t* __restrict__ list_n, int32_t cap, AttrArgs<kAttr> fa) {
+    int32_t* __restrict__ list_n, int32_t cap, AttrArgs<kAttr> fa, BoostArgs<kBoost> fb) {
     using Tile = ScoreTile<D>;
     __shared__ float cs[2][Tile::kLdsFloats];
     __shared__ uint32_t wh[kAttr ? 4 : 1][96];  // (any, all, none) of each wave's 32 queries
@@ -90,6 +99,17 @@ __global__ __launch_bounds__(kBlock, ScoreTile<D>::kWaves) void k_score_filter(
         return 0u;
     };
     [[maybe_unused]] uint32_t at = 0u, at_nxt = 0u;
+    // ... and its boost
+    [[maybe_unused]] auto boost_of = [&](int64_t b) -> float {
+        const int64_t j = b * 32 + i;
+        if constexpr (kBoost) return j < M ? fb.boost[j * stride] : 0.f;
+        return 0.f;
+    };
+    [[maybe_unused]] float bo = 0.f, bo_nxt = 0.f;
+    // kBoost: the wave's real query rows are [0, nv). th = +inf keeps a padding row's plain score out, but
+    // not a +inf or NaN sum (!(sc < +inf) holds for both), so a boosted kernel tests the row as well.
+    [[maybe_unused]] const int64_t left = Qvalid - q0;
+    [[maybe_unused]] const int nv = left >= 32 ? 32 : left <= 0 ? 0 : static_cast<int>(left);
     int scnt = 0;  // wave-uniform staged count
     const unsigned long long below = (1ull << lane) - 1ull;
     // flush (wave-uniform): ranks within each query row from LDS atomics (list order does not
@@ -122,6 +142,7 @@ __global__ __launch_bounds__(kBlock, ScoreTile<D>::kWaves) void k_score_filter(
     if (cb < nblk) {
         tile.fetch(Cn, M, stride, cb);
         if constexpr (kAttr) at = attr_of(cb);
+        if constexpr (kBoost) bo = boost_of(cb);
         tile.land(cs, 0);
     }
     __syncthreads();
@@ -131,6 +152,7 @@ __global__ __launch_bounds__(kBlock, ScoreTile<D>::kWaves) void k_score_filter(
         if (nxt < nblk) {  // in flight during this block's MFMAs
             tile.fetch(Cn, M, stride, nxt);
             if constexpr (kAttr) at_nxt = attr_of(nxt);
+            if constexpr (kBoost) bo_nxt = boost_of(nxt);
         }
         const f32x16 acc = tile.scores(cs, buf);
         // epilogue: column = candidate j (this lane's), rows = queries; branch-free test, and
@@ -141,14 +163,17 @@ __global__ __launch_bounds__(kBlock, ScoreTile<D>::kWaves) void k_score_filter(
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int row = Tile::row(r, h);
-            bool take = jok & !(acc[r] < th[r]);
+            float sc = acc[r];
+            if constexpr (kBoost) sc = __fadd_rn(sc, bo);
+            bool take = jok & !(sc < th[r]);
+            if constexpr (kBoost) take &= row < nv;
             if constexpr (kAttr) {
                 if (__ballot(take) == 0ull) continue;
                 const uint32_t* w = &wh[wv][row * 3];
                 take &= attr_passes(at, w[0], w[1], w[2]);
             }
             if (!kAttr && thr == nullptr) {  // dense mode: every subset score at its subset slot
-                const uint32_t key = score_key(acc[r]);
+                const uint32_t key = score_key(sc);
                 if (take) {
                     const int64_t q = q0 + row;
                     list_key[q * cap + j] = key;
@@ -162,7 +187,7 @@ __global__ __launch_bounds__(kBlock, ScoreTile<D>::kWaves) void k_score_filter(
             if (scnt + n > kStage) flush();
             if (take) {
                 const int sl = scnt + __popcll(m & below);
-                st_key[wv][sl] = score_key(acc[r]);
+                st_key[wv][sl] = score_key(sc);
                 st_idx[wv][sl] = jj;
                 st_row[wv][sl] = static_cast<uint8_t>(row);
             }
@@ -172,6 +197,7 @@ __global__ __launch_bounds__(kBlock, ScoreTile<D>::kWaves) void k_score_filter(
         __syncthreads();
         buf ^= 1;
         if constexpr (kAttr) at = at_nxt;
+        if constexpr (kBoost) bo = bo_nxt;
     }
     if (kAttr || thr != nullptr) flush();
 }
@@ -397,11 +423,11 @@ __global__ __launch_bounds__(kSelBlock) void k_select_ranked(
     if (tid == 0) out_n[q] = W;
 }
 
-template <int D, bool kAttr = false>
+template <int D, bool kAttr = false, bool kBoost = false>
 int launch_filter(const float* Qn, int64_t Qpad, int64_t Qvalid, const float* Cn, int64_t M, int64_t stride,
                   const uint32_t* thr, uint32_t* lk, int32_t* li, int32_t* ln, int32_t cap, hipStream_t s,
-                  const uint32_t* attr = nullptr, const uint32_t* where = nullptr) {
-    const char* me = kAttr ? "lgcn_score_filter_attr" : "lgcn_score_filter";
+                  const uint32_t* attr = nullptr, const uint32_t* where = nullptr, const float* boost = nullptr) {
+    const char* me = kBoost ? "lgcn_score_filter_boost" : kAttr ? "lgcn_score_filter_attr" : "lgcn_score_filter";
     if (Qpad % kTileQueries != 0)
         return fail(LGCN_E_ARG, "%s: padded query count %lld not a multiple of %d", me, (long long)Qpad, kTileQueries);
     const int64_t nqg = Qpad / kTileQueries;
@@ -410,9 +436,12 @@ int launch_filter(const float* Qn, int64_t Qpad, int64_t Qvalid, const float* Cn
     if (!score_grid(nqg, M, nchunk, grid)) return fail(LGCN_E_ARG, "%s: too many queries", me);
     AttrArgs<kAttr> fa;
     if constexpr (kAttr) fa = {attr, where};
-    k_score_filter<D, kAttr><<<dim3(grid), kBlock, 0, s>>>(Qn, Qvalid, static_cast<int32_t>(nqg), nchunk, Cn, M, stride,
-                                                           thr, lk, li, ln, cap, fa);
-    return check_launch(kAttr ? "k_score_filter<attr>" : "k_score_filter");
+    BoostArgs<kBoost> fb;
+    if constexpr (kBoost) fb = {boost};
+    k_score_filter<D, kAttr, kBoost><<<dim3(grid), kBlock, 0, s>>>(Qn, Qvalid, static_cast<int32_t>(nqg), nchunk, Cn, M,
+                                                                   stride, thr, lk, li, ln, cap, fa, fb);
+    return check_launch(kBoost ? (kAttr ? "k_score_filter<attr, boost>" : "k_score_filter<boost>")
+                               : kAttr ? "k_score_filter<attr>" : "k_score_filter");
 }
 
 

@@ -31,6 +31,20 @@ __device__ __forceinline__ uint32_t score_key(float s) { return s != s ? 0xFFFFF
 // inverse of score_key (the NaN key maps back to a NaN)
 __device__ __forceinline__ float key_score(uint32_t k) { return ordered_value(k); }
 
+// Per-candidate score boosts (lgcn_score_filter_boost, lgcn_score_lists_boost): a boosted kernel's one
+// extra argument, and nothing at all in the unboosted instantiation (an empty record takes no kernel
+// argument, so that one keeps the argument block it had).
+template <bool kBoost>
+struct BoostArgs {};
+template <>
+struct BoostArgs<true> {
+    const float* boost;  // [M] f32, by candidate index
+};
+
+// the key of a boosted pair: ONE IEEE f32 addition (the library is built with -ffp-contract=off),
+// then the key of the sum. b = -0.0 gives score_key(s) for every s, NaN and -0 included.
+__device__ __forceinline__ uint32_t boosted_key(float s, float b) { return score_key(__fadd_rn(s, b)); }
+
 constexpr int kTileQueries = 4 * 32;  // queries per workgroup
 
 template <int D>

@@ -169,6 +169,10 @@ _SIGS = {
     "lgcn_rank_positions": ([_vp, _i64, _i64, _vp, _i64, _i32, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _i64,
                              _vp, _vp, _vp, _vp, _sz, _i32, _vp], ctypes.c_int),
     "lgcn_score_lists": ([_vp, _i64, _vp, _i64, _i32, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i32, _vp], ctypes.c_int),
+    "lgcn_score_filter_boost": ([_vp, _i64, _i64, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp],
+                                ctypes.c_int),
+    "lgcn_score_lists_boost": ([_vp, _i64, _vp, _i64, _i32, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i32, _vp, _vp],
+                               ctypes.c_int),
     "lgcn_score_filter_groups": ([_vp, _i64, _i64, _i32, _vp, _i32, _vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _i32,
                                   _vp], ctypes.c_int),
     "lgcn_legacy_choice": ([_vp, _vp, _i64, _i64, _i64, _vp], ctypes.c_int),
@@ -264,10 +268,10 @@ def load(path: os.PathLike | str | None = None) -> ctypes.CDLL:
 CSRC = _HERE.parent / "csrc"
 INCLUDE = _HERE.parent.parent / "include"
 # the translation units of liblgcn.so (lgcn_build.cpp carries the hash and is not hashed)
-SOURCES = ("lgcn_plan.hip", "lgcn_spmm.hip", "lgcn_optim.hip", "lgcn_bpr.hip", "lgcn_recall.hip", "lgcn_recall_attr.hip", "lgcn_recall_among.hip", "lgcn_recall_group.hip", "lgcn_metrics.hip", "lgcn_rerank.hip",
+SOURCES = ("lgcn_plan.hip", "lgcn_spmm.hip", "lgcn_optim.hip", "lgcn_bpr.hip", "lgcn_recall.hip", "lgcn_recall_attr.hip", "lgcn_recall_among.hip", "lgcn_recall_boost.hip", "lgcn_recall_group.hip", "lgcn_metrics.hip", "lgcn_rerank.hip",
            "lgcn_explain.hip", "lgcn_foldin.hip", "lgcn_calibrate.hip", "lgcn_negatives.hip", "lgcn_rankpos.hip", "lgcn_rowadam.hip", "lgcn_exchange.hip", "lgcn_partition.cpp", "lgcn_sample.cpp", "lgcn_tuning.cpp", "lgcn_program.cpp")
 # the headers they include (csrc/), hashed and tracked as build dependencies with include/lgcn.h
-HEADERS = ("lgcn_common.h", "lgcn_exact.h", "lgcn_reg.h", "lgcn_ragged.h", "lgcn_scoretile.h", "lgcn_recall_lists.h")
+HEADERS = ("lgcn_common.h", "lgcn_exact.h", "lgcn_reg.h", "lgcn_ragged.h", "lgcn_scoretile.h", "lgcn_recall_lists.h", "lgcn_recall_among.h")
 
 
 def source_sha256() -> str:

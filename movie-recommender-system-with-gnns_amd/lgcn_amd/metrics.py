@@ -159,7 +159,8 @@ def evaluate_ranking(user_emb: torch.Tensor, item_emb: torch.Tensor, truth, ks=(
     user, seen's convention: a 2-tuple is a CSR over all users, a 3-tuple names each evaluated user's
     row; the metrics of the lists ranked among the sets — the sampled-negative protocol's numbers
     when a set is the user's held-out items and sampled negatives; a re-rank pool then holds set
-    entries only).
+    entries only) and boost (one f32 per item added to every user's scores, recommend.popularity_boost's
+    penalty for one: the metrics of the boosted lists, re-ranked ones included, against the same truth).
     One recommend.topk_items call for max(ks) items per user, one lgcn_rank_metrics launch, then
     summarize. Host reads: summarize's one; topk_rows' one per query block when the items exceed
     its dense capacity; and, when ``users`` is left to default, the size of torch.nonzero's result

@@ -24,6 +24,14 @@ any point and the host reads at most one value pair per query block.
                  ranked emit             lgcn_select_topk_ranked[_attr]
     and the list is the query's full ranking restricted to its row, bit for bit.
 
+    with boost= (one f32 per candidate: "show less of what everybody has seen", a lift for new releases,
+    a second model's item bias; popularity_boost makes the first from interaction counts) every call
+    above that forms a key is its _boost twin — lgcn_score_filter_boost for the dense rows, the subset
+    and the lists (with the attribute filter or without), lgcn_score_lists_boost for among — and the key
+    of a pair is that of score + boost[j], one f32 addition (csrc/lgcn_recall_boost.hip). The thresholds,
+    the tightening and the ranked selection read keys and run as they are, so a strongly boosted
+    candidate is found wherever it stood in the unboosted ranking; the returned score is the boosted one.
+
     topk_groups (one list for several query rows: "what do the four of us watch tonight?") runs the same
     dense / filtered blocks with a "query" meaning a group of S member rows (S = 2 .. 32, one plan per size
     class): lgcn_score_filter_groups (csrc/lgcn_recall_group.hip) reduces a candidate's member scores
@@ -34,7 +42,8 @@ any point and the host reads at most one value pair per query block.
 On the host topk_rows is one prepared plan and three block strategies. It checks every argument
 before the library is loaded, then builds a _Plan: the query order (the caller's, or the among
 sort), Qn and Cn, the output buffers, the exclusion CSR and the attribute table on the device, and
-the only two places that choose between a kernel and its _attr twin (_Plan.filter, _Plan.select).
+the only two places that choose between a kernel and its _attr or _boost twin (_Plan.filter,
+_Plan.select).
 _run_dense, _run_filtered and _run_among are the three blocks of the table above, written over the
 plan; _Plan.finish puts the lists back in the caller's order and gives them their index dtype. The
 pieces that other modules need too (row lengths, a CSR argument's device tensors and block
@@ -175,6 +184,41 @@ def _where_arg(attrs, where, M: int, Q: int):
     cols = [_mask_column(n, m, Q) for n, m in zip(("any", "all", "none"), where)]
     dev = next((c.device for c in cols if c.is_cuda), torch.device("cpu"))
     return torch.stack([c.to(dev).expand(Q) for c in cols], 1).to(torch.int32)
+
+
+def _boost_arg(boost, M: int, device) -> None:
+    """topk_rows' boost, checked (nothing is read): None, or a float32 tensor [M] on ``device``."""
+    if boost is None:
+        return
+    if not isinstance(boost, torch.Tensor) or boost.dtype != torch.float32:
+        raise ValueError(f"recommend: boost must be a float32 tensor [M], got "
+                         f"{boost.dtype if isinstance(boost, torch.Tensor) else type(boost).__name__}")
+    if boost.dim() != 1 or boost.numel() != M:
+        raise ValueError(f"recommend: boost has shape {tuple(boost.shape)} for {M} candidates, not [{M}]")
+    if boost.device != device:
+        raise ValueError(f"recommend: boost is on {boost.device}, the queries on {device}")
+
+
+def popularity_boost(counts: torch.Tensor, strength: float) -> torch.Tensor:
+    """A popularity penalty for topk_rows' boost=: float32 [M] on counts' device,
+    -strength * log1p(counts) / log1p(counts.max()), formed in float64 and rounded once. It is 0 for
+    an item nobody has touched and -strength for the most popular one, the logarithm in between (the
+    counts of a catalogue span orders of magnitude). strength is on the cosine's scale, [-1, 1]: 0.2
+    takes a fifth of the score range off the most popular item; a negative strength lifts popular
+    items instead. counts: interaction counts per item, any real dtype, non-negative (the lengths of
+    seen_csr(..., by="item") rows). An all-zero counts gives zeros. Plain torch ops; nothing is read on
+    the host."""
+    if not isinstance(counts, torch.Tensor) or counts.dim() != 1 or counts.dtype == torch.bool or counts.is_complex():
+        raise TypeError("popularity_boost: counts must be a 1-D tensor of counts")
+    strength = float(strength)
+    if strength != strength:
+        raise ValueError("popularity_boost: strength is NaN")
+    if counts.numel() == 0:
+        return torch.zeros(0, dtype=torch.float32, device=counts.device)
+    logs = torch.log1p(counts.detach().to(torch.float64))
+    top = logs.max()
+    share = torch.where(top > 0, logs / top.clamp(min=torch.finfo(torch.float64).tiny), torch.zeros_like(logs))
+    return (-strength * share).to(torch.float32)
 
 
 def candidate_csr(lists, device=None):
@@ -324,10 +368,11 @@ class _Plan:
     mask table and the outputs are per group, and select and the strategies run as they are."""
 
     def __init__(self, lib, queries, picked, candidates, k: int, D: int, Qpad: int, excl, masks, attrs, order=None,
-                 group=None, Cn=None):
+                 group=None, Cn=None, boost=None):
         dev = queries.device
         self.lib, self.dev, self.s = lib, dev, _ffi.stream_of(dev)
         self.group, self.rows = group, 1 if group is None else group.S  # member rows per query
+        self.boost = None if boost is None else boost.detach().contiguous()  # f32 [M]: filter's and _run_among's
         self.qmul = _serving.QUERY_MULTIPLE // self.rows
         self.k, self.D, self.Qpad, self.M, self.order = k, D, Qpad, candidates.shape[0], order
         self.Q = picked.numel() // self.rows
@@ -377,7 +422,8 @@ class _Plan:
     def filter(self, q0: int, nb: int, qv: int, n: int, stride: int, cap: int, what: str, thr=None, counts=None) -> None:
         """Score the block's queries against n candidates ``stride`` apart into the lists: every score
         in candidate order (thr None), or the scores at or above the thresholds, counted; under an
-        attribute filter only candidates that pass enter a thresholded list.
+        attribute filter only candidates that pass enter a thresholded list. With a boost every one of
+        these passes is lgcn_score_filter_boost's (labelled as ``what`` with the _boost name).
         Group mode: the group keys of lgcn_score_filter_groups. It does not know the attribute predicate
         (select alone applies it), and under a floor "every score" is a list under zero thresholds,
         counted in fcnt, which select then reads in place of dense rows: a dense row cannot say that a
@@ -398,7 +444,11 @@ class _Plan:
         qptr = self.Qn.data_ptr() + q0 * self.D * 4
         args = (qptr, nb, qv, self.Cn.data_ptr(), n, stride, self.D, thr, self.lkey.data_ptr(), self.lidx.data_ptr(),
                 counts, cap)
-        if thr is None or self.wh is None:
+        if self.boost is not None:  # every pass forms boosted keys; dense rows take no attribute filter
+            wh = (None, None) if thr is None or self.wh is None else (self.attrs.data_ptr(), self.wh.data_ptr() + q0 * 12)
+            _ffi.check(self.lib.lgcn_score_filter_boost(*args, *wh, self.boost.data_ptr(), self.s),
+                       what.replace("lgcn_score_filter", "lgcn_score_filter_boost"))
+        elif thr is None or self.wh is None:
             _ffi.check(self.lib.lgcn_score_filter(*args, self.s), what)
         else:
             _ffi.check(self.lib.lgcn_score_filter_attr(*args, self.attrs.data_ptr(), self.wh.data_ptr() + q0 * 12, self.s),
@@ -484,15 +534,18 @@ def _run_among(plan: _Plan, among, blocks) -> None:
     plan.lists(max((b - a) * cap for a, b, cap in blocks))  # one pair of list buffers serves every block
     for a, b, cap in blocks:
         counts = lcnt.data_ptr() + a * 4
-        _ffi.check(plan.lib.lgcn_score_lists(plan.Qn.data_ptr() + a * plan.D * 4, b - a, plan.Cn.data_ptr(), plan.M, plan.D,
-                                             *_serving.csr_at(aptr, aidx, arow, a), plan.lkey.data_ptr(),
-                                             plan.lidx.data_ptr(), counts, cap, plan.s), "lgcn_score_lists")
+        args = (plan.Qn.data_ptr() + a * plan.D * 4, b - a, plan.Cn.data_ptr(), plan.M, plan.D,
+                *_serving.csr_at(aptr, aidx, arow, a), plan.lkey.data_ptr(), plan.lidx.data_ptr(), counts, cap)
+        if plan.boost is None:
+            _ffi.check(plan.lib.lgcn_score_lists(*args, plan.s), "lgcn_score_lists")
+        else:
+            _ffi.check(plan.lib.lgcn_score_lists_boost(*args, plan.boost.data_ptr(), plan.s), "lgcn_score_lists_boost")
         plan.select(a, b - a, b - a, counts, _ffi.RANKED_REPEATS, cap, emit=True)
 
 
 def topk_rows(queries: torch.Tensor, picked: torch.Tensor, candidates: torch.Tensor, k: int, excl=None,
               cap: int | None = None, subset: int | None = None, index_dtype: torch.dtype = torch.int64,
-              attrs: torch.Tensor | None = None, where=None, among=None):
+              attrs: torch.Tensor | None = None, where=None, among=None, boost: torch.Tensor | None = None):
     """(idx [Q, k] of ``index_dtype``, int64 by default; score f32 [Q, k]) on the device: for query
     row queries[picked[q]], the k best rows of ``candidates`` by cosine score that its exclusion row
     does not name, in rank order (score descending, candidate index ascending; NaN first).
@@ -532,7 +585,20 @@ def topk_rows(queries: torch.Tensor, picked: torch.Tensor, candidates: torch.Ten
     max(k, the block's longest row), at most BLOCK_BYTES // (8 * capacity) queries each, and come
     back in the caller's order; the row lengths are read on the host once per call. A row longer
     than _ffi.RANKED_MAX_CAP is a ValueError naming the length; cap= and subset= have no meaning
-    with among and passing either is a ValueError."""
+    with among and passing either is a ValueError.
+    boost: None, or a float32 tensor [M] on the queries' device, one value per candidate, shared by all
+    queries (a per-query weight is the caller's scaling of the vector): candidate j is ranked by
+    score + boost[j], ONE f32 addition on the score the unboosted call gives the pair, and that sum is
+    the score returned. It is added where the key is formed, before any threshold, so a boosted
+    candidate is found wherever it stood before; everything else — the order, excl, attrs / where,
+    among, the padding, cap's meaning — is unchanged, on the boosted scores. -0.0 is the exact identity
+    (the unboosted lists, bit for bit, at the boosted kernels' cost); -inf ranks a candidate last among
+    the eligible, where it still fills a slot when fewer than k others exist; +inf ranks it above every
+    finite score; NaN first. Nothing is checked on the values and no host read is added. Any other
+    dtype, shape or device is a ValueError before anything is launched. With boost=None the library
+    calls are exactly those above. popularity_boost makes a popularity penalty from interaction counts.
+    topk_items, topk_users, topk_rows_diverse, topk_rows_calibrated and metrics.evaluate_ranking hand
+    boost= on; topk_groups and metrics.rank_positions / evaluate_auc do not take one."""
     k = int(k)
     if index_dtype not in (torch.int64, torch.int32):
         raise ValueError(f"recommend: index_dtype must be torch.int64 or torch.int32, got {index_dtype}")
@@ -554,6 +620,7 @@ def topk_rows(queries: torch.Tensor, picked: torch.Tensor, candidates: torch.Ten
         if subset < 1:
             raise ValueError(f"recommend: subset={subset}")
     masks = _where_arg(attrs, where, candidates.shape[0], Q)
+    _boost_arg(boost, candidates.shape[0], queries.device)
     if excl is not None:
         excl = _serving.csr_arg("recommend", "excl", excl, Q)[:3]
     order = blocks = None
@@ -579,10 +646,10 @@ def topk_rows(queries: torch.Tensor, picked: torch.Tensor, candidates: torch.Ten
         return (torch.empty((0, k), dtype=index_dtype, device=dev),
                 torch.empty((0, k), dtype=torch.float32, device=dev))
     if among is not None:  # unpadded: a block is launched for its own queries only
-        plan = _Plan(lib, queries, picked, candidates, k, D, Q, excl, masks, attrs, order.to(dev))
+        plan = _Plan(lib, queries, picked, candidates, k, D, Q, excl, masks, attrs, order.to(dev), boost=boost)
         _run_among(plan, among, blocks)
     else:
-        plan = _Plan(lib, queries, picked, candidates, k, D, _serving.padded(Q), excl, masks, attrs)
+        plan = _Plan(lib, queries, picked, candidates, k, D, _serving.padded(Q), excl, masks, attrs, boost=boost)
         if candidates.shape[0] <= cap:
             _run_dense(plan)
         else:
@@ -776,9 +843,10 @@ def topk_rows_diverse(queries: torch.Tensor, picked: torch.Tensor, candidates: t
     pool: default max(4 * k, 64); whatever is asked for is clamped to what exists and what the
     re-rank kernel holds, min(M, MMR_MAX_POOL, MMR_MAX_LDS_BYTES // (4 * D)) with D the padded
     width, and a pool that ends up below k is a ValueError. excl and kw (cap, subset, index_dtype,
-    attrs, where, among) are topk_rows'; under a filter a query's pool holds passing candidates only,
-    and with among= entries of the query's row only (a pool wider than a row is padded, and the picks
-    all lie in the row)."""
+    attrs, where, among, boost) are topk_rows'; under a filter a query's pool holds passing candidates
+    only, and with among= entries of the query's row only (a pool wider than a row is padded, and the
+    picks all lie in the row). With boost= the pool is the boosted ranking's and the relevance MMR
+    weighs — and ``score`` — is the boosted score."""
     k, diversity = int(k), _diversity(diversity)
     if k < 1:
         raise ValueError(f"recommend: k={k} outside [1, {MMR_MAX_POOL}]")
@@ -956,8 +1024,10 @@ def topk_rows_calibrated(queries: torch.Tensor, picked: torch.Tensor, candidates
     (ptr, idx, rows), profiled here by attr_profile — and target (f32 [Q, 32]) says what to
     calibrate to. pool: default max(4 * k, 64); whatever is asked for is clamped to what exists and
     what the re-rank kernel holds, min(M, CALIB_MAX_POOL), and a pool that ends up below k is a
-    ValueError. excl and kw (where, among, cap, subset, index_dtype) are topk_rows'; under a filter a
-    query's pool holds passing candidates only, and with among= entries of the query's row only."""
+    ValueError. excl and kw (where, among, boost, cap, subset, index_dtype) are topk_rows'; under a filter
+    a query's pool holds passing candidates only, and with among= entries of the query's row only. With
+    boost= the pool is the boosted ranking's and the relevance the calibration weighs — and ``score`` —
+    is the boosted score."""
     k, calibration, alpha = int(k), _calibration(calibration), _alpha(alpha)
     if k < 1:
         raise ValueError(f"recommend: k={k} outside [1, {CALIB_MAX_POOL}]")
@@ -1010,7 +1080,8 @@ def miscalibration(kl: torch.Tensor, n: torch.Tensor, ks) -> torch.Tensor:
 def topk_items(user_emb: torch.Tensor, item_emb: torch.Tensor, users, k: int, seen=None, among=None, **kw):
     """The k best items for each user index in ``users``; seen: seen_csr(..., by="user") over all
     users (row u is user u's), whose items are left out. Returns topk_rows' (idx, score). kw: topk_rows'
-    cap, subset, index_dtype, attrs and where (the items' attribute words; one filter per user or one for all).
+    cap, subset, index_dtype, attrs and where (the items' attribute words; one filter per user or one for all)
+    and boost (one f32 per item).
     among: topk_rows' candidate sets with seen's convention — a 2-tuple (ptr, idx) is a CSR over all
     users, row u being user u's set; a 3-tuple names each query's row."""
     users = torch.as_tensor(users).view(-1)

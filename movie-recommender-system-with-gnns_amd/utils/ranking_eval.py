@@ -5,6 +5,9 @@ over every user with held-out items, on the HIP path of lgcn_amd.metrics.
     from utils.ranking_eval import evaluate_ranking
     evaluate_ranking(model, train_data.edge_index, test_data.edge_index, 'cuda', ks=(10, 20))
 
+evaluate_ranking_boosted is evaluate_ranking of the lists served under a per-item score boost or a
+popularity penalty (utils.recommend.recommend_for_users_boosted).
+
 evaluate_auc reports what the cutoffs hide: exact full-ranking AUC, mean percentile rank, MRR and
 mean rank of the held-out items (lgcn_amd.metrics.evaluate_auc), and the @c metrics at any cutoffs.
 
@@ -34,11 +37,25 @@ def evaluate_ranking(model: torch.nn.Module, train_edge_index: torch.Tensor, hel
     calibrated lists utils.recommend.recommend_for_users serves with the same argument, each user's
     target being the genre mix of their training items, and adds 'ckl@c' (the KL divergence between
     that mix and the list's) per cutoff; 0.0 only measures. The genre words come from
-    utils.recommend.genre_table(data_handler), or are given as attrs (int32 [num_items])."""
+    utils.recommend.genre_table(data_handler), or are given as attrs (int32 [num_items]).
+    evaluate_ranking_boosted is this call with a per-item score boost and a popularity penalty."""
+    return evaluate_ranking_boosted(model, train_edge_index, heldout_edge_index, device, ks=ks, embeddings=embeddings,
+                                    diversity=diversity, pool=pool, calibration=calibration, data_handler=data_handler,
+                                    attrs=attrs)
+
+
+def evaluate_ranking_boosted(model: torch.nn.Module, train_edge_index: torch.Tensor, heldout_edge_index: torch.Tensor,
+                             device, boost=None, less_popular=None, ks=(20,), embeddings: str = "raw", diversity=None,
+                             pool=None, calibration=None, data_handler=None, attrs=None) -> dict:
+    """evaluate_ranking of the lists utils.recommend.recommend_for_users_boosted serves with the same
+    arguments: boost a float tensor over the items (lgcn_amd.recommend.topk_rows' boost), less_popular a
+    float b adding lgcn_amd.recommend.popularity_boost(counts, b) of the items' interaction counts in
+    ``train_edge_index``. Both work with diversity and calibration, which then re-rank boosted scores;
+    every other argument and the returned dict are evaluate_ranking's."""
     if embeddings not in ("raw", "propagated"):
         raise ValueError(f"evaluate_ranking: embeddings must be 'raw' or 'propagated', got {embeddings!r}")
     from lgcn_amd import metrics
-    from lgcn_amd.recommend import seen_csr
+    from lgcn_amd.recommend import popularity_boost, seen_csr
 
     if calibration is None:
         if data_handler is not None or attrs is not None:
@@ -61,10 +78,21 @@ def evaluate_ranking(model: torch.nn.Module, train_edge_index: torch.Tensor, hel
                                                       item_indices=torch.arange(I, device=device))
         else:
             user_emb, item_emb = model(train_edge_index)
+        kw = {}
+        if boost is not None or less_popular is not None:
+            vec = None
+            if boost is not None:
+                if not isinstance(boost, torch.Tensor) or not boost.is_floating_point() or boost.shape != (I,):
+                    raise ValueError(f"evaluate_ranking: boost is a float tensor over the {I} items")
+                vec = boost.detach().to(device=user_emb.device, dtype=torch.float32)
+            if less_popular is not None:
+                penalty = popularity_boost(torch.bincount(seen[1].to(torch.int64), minlength=I), float(less_popular))
+                vec = penalty if vec is None else vec + penalty
+            kw["boost"] = vec.contiguous()
         if calibration is not None:
             return metrics.evaluate_ranking(user_emb, item_emb, truth, ks=ks, seen=seen, diversity=diversity, pool=pool,
-                                            calibration=calibration, attrs=attrs.to(device))
-        return metrics.evaluate_ranking(user_emb, item_emb, truth, ks=ks, seen=seen, diversity=diversity, pool=pool)
+                                            calibration=calibration, attrs=attrs.to(device), **kw)
+        return metrics.evaluate_ranking(user_emb, item_emb, truth, ks=ks, seen=seen, diversity=diversity, pool=pool, **kw)
 
 
 def evaluate_auc(model: torch.nn.Module, train_edge_index: torch.Tensor, heldout_edge_index: torch.Tensor,

@@ -28,6 +28,13 @@ the user's own history — 70 % drama and 30 % comedy watched, about that served
 a relevance pool against the KL divergence between the two genre distributions, on the device
 (lgcn_amd.recommend.topk_rows_calibrated; ``python utils/recommend.py USER_ID --calibrate 0.5``, likewise
 with ``--movies``).
+``boost=`` / ``less_popular=`` (recommend_for_users_boosted, recommend_for_histories_boosted: the two
+batch calls with two more arguments) move scores instead of
+choosing candidates: a value per movie added to its score before anything is ranked — a lift for this
+month's releases, a title buried without being removed, a second model's item bias — and a penalty on
+popular movies, ``less_popular`` times the movie's share of the log of the highest training interaction
+count (lgcn_amd.recommend.topk_rows' boost and popularity_boost, on the device;
+``python utils/recommend.py USER_ID --less-popular 0.2``, likewise with ``--movies``).
 ``recommend_for_groups`` / ``recommend_for_group`` serve several users ONE list — "what do the four of us
 watch tonight?" — by least misery (the minimum of the members' scores), most pleasure (the maximum) or
 the average, optionally without anything a member scores under a floor; the members' scores are reduced
@@ -143,6 +150,34 @@ def _among_csr(who: str, among, inputs: int, served, handler: Any, device):
             ptr, idx = _rec.candidate_csr([known(among)], device=device)
             return {"among": (ptr, idx, torch.zeros(len(served), dtype=torch.int64))}
     return {"among": _rec.candidate_csr(rows, device=device)}
+
+
+def _boost_vector(who: str, handler: Any, boost, less_popular, counts, device) -> dict:
+    """topk_rows' boost= of one call, {} when both arguments are None: float32 [num_items] on ``device``.
+    boost: a float tensor over the items (item-index order), or a mapping MovieLens movie id -> value
+    with the movies it does not name at -0.0, the exact identity (unknown ids are dropped).
+    less_popular: a float b, adding lgcn_amd.recommend.popularity_boost(counts(), b); counts: a function
+    that returns the training interaction count per item (called only when it is needed)."""
+    if boost is None and less_popular is None:
+        return {}
+    num_users, num_items = len(handler.user_id_map), len(handler.movie_id_map)
+    vec = None
+    if isinstance(boost, Mapping):
+        host = torch.full((num_items,), -0.0, dtype=torch.float32)
+        for movie_id, value in boost.items():
+            if movie_id in handler.movie_id_map:
+                host[handler.movie_id_map[movie_id] - num_users] = float(value)
+        vec = host.to(device)
+    elif boost is not None:
+        if not isinstance(boost, torch.Tensor) or not boost.is_floating_point() or boost.dim() != 1:
+            raise ValueError(f"{who}: boost is a float tensor over the items or a mapping movie id -> value")
+        if boost.numel() != num_items:
+            raise ValueError(f"{who}: boost has {boost.numel()} values for {num_items} movies")
+        vec = boost.detach().to(device=device, dtype=torch.float32)
+    if less_popular is not None:
+        penalty = _rec.popularity_boost(counts().to(device), float(less_popular))
+        vec = penalty if vec is None else vec + penalty
+    return {"boost": vec.contiguous()}
 
 
 def _cli_option(argv: List[str], flag: str) -> Optional[List[str]]:
@@ -306,7 +341,35 @@ def recommend_for_users(model: torch.nn.Module, user_ids: Sequence[int], data_ha
     edge set ``exclude_seen`` uses, whether or not it is set; genre_table's words, a movie's genres
     sharing its weight equally), in pick order; 0.0 is the relevance list, 1.0 follows the genre mix
     alone. 'score' stays the cosine relevance. It works beside the genre arguments, ``among`` and
-    ``explain``, and not with ``diversity`` (ValueError: one re-rank per call)."""
+    ``explain``, and not with ``diversity`` (ValueError: one re-rank per call).
+    recommend_for_users_boosted is this call with two more arguments, a per-movie score boost and a
+    popularity penalty; this one is that one without them."""
+    return recommend_for_users_boosted(model, user_ids, data_handler, k=k, exclude_seen=exclude_seen,
+                                       train_edge_index=train_edge_index, diversity=diversity, pool=pool, explain=explain,
+                                       genres=genres, genres_all=genres_all, without_genres=without_genres, among=among,
+                                       calibration=calibration)
+
+
+def recommend_for_users_boosted(model: torch.nn.Module, user_ids: Sequence[int], data_handler: Any, boost=None,
+                                less_popular: Optional[float] = None, k: int = 10, exclude_seen: bool = True,
+                                train_edge_index: Optional[torch.Tensor] = None, diversity: Optional[float] = None,
+                                pool: Optional[int] = None, explain: Optional[int] = None,
+                                genres: Optional[Sequence[str]] = None, genres_all: Optional[Sequence[str]] = None,
+                                without_genres: Optional[Sequence[str]] = None, among=None,
+                                calibration: Optional[float] = None
+                                ) -> List[Union[Dict[str, str], List[Dict[str, Any]]]]:
+    """recommend_for_users with the scores moved before anything is ranked; every other argument and the
+    returned entries are recommend_for_users'.
+    ``boost`` (None: recommend_for_users' calls and dictionaries) adds a value to a movie's score for every user before
+    anything is ranked: a float tensor over the items in item-index order, or a mapping
+    {MovieLens movie id: value} whose unnamed movies get -0.0, which changes nothing. 'score' is the
+    boosted score. -inf buries a movie (it is served only when nothing else is left), a positive value
+    lifts one; the scale is the cosine's. ``less_popular`` (a float b; None: nothing) adds
+    lgcn_amd.recommend.popularity_boost of the movies' interaction counts in the edge set
+    ``exclude_seen`` uses (whether or not it is set): 0 for a movie nobody has an edge to, -b for the one
+    most have, the logarithm of the count in between. Both may be given (they add) and both work beside
+    the genre arguments, ``among``, ``diversity``, ``calibration`` (the re-ranks then weigh the boosted
+    score) and ``explain``."""
     explain = _check_options("recommend_for_users", diversity, pool, explain, calibration)
     flt = _genre_filter("recommend_for_users", data_handler, genres, genres_all, without_genres)
     user_id_map, movie_id_map = data_handler.user_id_map, data_handler.movie_id_map
@@ -322,17 +385,20 @@ def recommend_for_users(model: torch.nn.Module, user_ids: Sequence[int], data_ha
     flt.update(_among_csr("recommend_for_users", among, len(user_ids), [(slot, user_ids[slot]) for slot, _ in known],
                           data_handler, dev))
     excl = history = None
-    if exclude_seen or explain is not None or calibration is not None:
+    if exclude_seen or explain is not None or calibration is not None or less_popular is not None:
         ei = data_handler.edge_index if train_edge_index is None else train_edge_index
         history = _rec.seen_csr(ei.to(dev), num_users, num_items, by="user")
         if exclude_seen:
             excl = (history[0], history[1], users)
+    flt.update(_boost_vector("recommend_for_users", data_handler, boost, less_popular,
+                             lambda: torch.bincount(history[1].to(torch.int64), minlength=num_items), dev))
     with torch.no_grad():
         user_emb, item_emb = model.get_embeddings(user_indices=users, item_indices=torch.arange(num_items, device=dev))
     why = None if explain is None else (lambda idx: _explain.explain_items(item_emb, users, idx, history, r=explain))
     profile = None if calibration is None else ((history[0], history[1], users), None)
     return _serve(data_handler, out, [slot for slot, _ in known], user_emb, item_emb, k, excl, diversity, pool, flt, why,
                   calibration, profile)
+
 
 
 def recommend_for_histories(model: torch.nn.Module, histories: Sequence[Sequence[int]], data_handler: Any, k: int = 10,
@@ -364,7 +430,29 @@ def recommend_for_histories(model: torch.nn.Module, histories: Sequence[Sequence
     ``among`` is recommend_for_users': one sequence of ids for every history, a sequence of id sequences
     aligned with ``histories``, or a mapping from a history's position to its ids.
     ``calibration`` is recommend_for_users', the target being the genre mix of the supplied history
-    (under its ``weights``)."""
+    (under its ``weights``).
+    recommend_for_histories_boosted is this call with a per-movie score boost and a popularity penalty."""
+    return recommend_for_histories_boosted(model, histories, data_handler, k=k, exclude_history=exclude_history,
+                                           train_edge_index=train_edge_index, embeddings=embeddings, weights=weights,
+                                           diversity=diversity, pool=pool, explain=explain, genres=genres,
+                                           genres_all=genres_all, without_genres=without_genres, among=among,
+                                           calibration=calibration)
+
+
+def recommend_for_histories_boosted(model: torch.nn.Module, histories: Sequence[Sequence[int]], data_handler: Any,
+                                    boost=None, less_popular: Optional[float] = None, k: int = 10,
+                                    exclude_history: bool = True, train_edge_index: Optional[torch.Tensor] = None,
+                                    embeddings: str = "raw", weights: Optional[Sequence[Sequence[float]]] = None,
+                                    diversity: Optional[float] = None, pool: Optional[int] = None,
+                                    explain: Optional[int] = None, genres: Optional[Sequence[str]] = None,
+                                    genres_all: Optional[Sequence[str]] = None,
+                                    without_genres: Optional[Sequence[str]] = None, among=None,
+                                    calibration: Optional[float] = None
+                                    ) -> List[Union[Dict[str, str], List[Dict[str, Any]]]]:
+    """recommend_for_histories with the scores moved before anything is ranked: ``boost`` and
+    ``less_popular`` are recommend_for_users_boosted's, the interaction counts being the movies' users in
+    ``train_edge_index`` (the degrees the fold-in divides by); every other argument and the returned entries
+    are recommend_for_histories'."""
     if embeddings not in ("raw", "propagated"):
         raise ValueError(f"recommend_for_histories: embeddings must be 'raw' or 'propagated', got {embeddings!r}")
     explain = _check_options("recommend_for_histories", diversity, pool, explain, calibration)
@@ -401,6 +489,7 @@ def recommend_for_histories(model: torch.nn.Module, histories: Sequence[Sequence
     ei = (data_handler.edge_index if train_edge_index is None else train_edge_index).to(dev)
     by_item = _rec.seen_csr(ei, num_users, num_items, by="item")
     degree = by_item[0][1:] - by_item[0][:-1]
+    flt.update(_boost_vector("recommend_for_histories", data_handler, boost, less_popular, lambda: degree, dev))
     with torch.no_grad():
         if embeddings == "raw":
             item_emb = model.get_embeddings(item_indices=torch.arange(num_items, device=dev))[1]
@@ -413,6 +502,7 @@ def recommend_for_histories(model: torch.nn.Module, histories: Sequence[Sequence
     why = None if explain is None else (lambda idx: _explain.explain_rows(idx, history, item_emb, r=explain))
     return _serve(data_handler, out, slots, queries, item_emb, k, history if exclude_history else None, diversity, pool,
                   flt, why, calibration, None if calibration is None else (history, hw))
+
 
 
 def recommend_for_groups(model: torch.nn.Module, groups_of_user_ids: Sequence[Sequence[int]], data_handler: Any,
@@ -531,6 +621,9 @@ if __name__ == '__main__':
                     among=_cli_ids(option('--among')))
     calibrate = option('--calibrate')  # a list that keeps the history's genre mix: --calibrate 0.5
     genre_kw['calibration'] = None if calibrate is None else float(calibrate[0])
+    less_popular = option('--less-popular')  # a penalty on popular movies: --less-popular 0.2
+    less_popular = None if less_popular is None else float(less_popular[0])
+    genre_kw['less_popular'] = less_popular  # counts as a filter below: the batch call serves the list
     filtered = any(v is not None for v in genre_kw.values())
     group = _cli_ids(option('--group'))
     strategy = (option('--strategy') or ['least_misery'])[0]
@@ -543,7 +636,7 @@ if __name__ == '__main__':
     model.eval()
     if len(sys.argv) > 2 and sys.argv[1] == '--movies':  # someone the model never saw: --movies 1,296,318
         watched = [int(m) for m in sys.argv[2].split(',') if m.strip()]
-        served = recommend_for_histories(model, [watched], handler, k=TOP_N, explain=3, **genre_kw)[0]
+        served = recommend_for_histories_boosted(model, [watched], handler, k=TOP_N, explain=3, **genre_kw)[0]
         if isinstance(served, dict):
             sys.exit(served['error'])
         print(f"Top 10 Recommendations for someone who watched {', '.join(map(str, watched))}:")
@@ -558,6 +651,8 @@ if __name__ == '__main__':
             sys.exit("--among is not supported with --group")
         if genre_kw.pop('calibration') is not None:
             sys.exit("--calibrate is not supported with --group")
+        if genre_kw.pop('less_popular') is not None:
+            sys.exit("--less-popular is not supported with --group")
         train_data, _, _ = handler.get_datasets()
         served = recommend_for_group(model, group, handler, k=TOP_N, strategy=strategy, floor=group_floor,
                                      train_edge_index=train_data.edge_index, **genre_kw)
@@ -581,7 +676,7 @@ if __name__ == '__main__':
             print(f"{r['movie_id']}: {r['title'] or '?'}: {where}")
         sys.exit(0)
     seen_items = ei[1, ei[0] == handler.user_id_map[uid]] - handler.num_users
-    why = recommend_for_users(model, [uid], handler, k=TOP_N, train_edge_index=ei, explain=3, **genre_kw)[0]
+    why = recommend_for_users_boosted(model, [uid], handler, k=TOP_N, train_edge_index=ei, explain=3, **genre_kw)[0]
     # the reference's own call serves the unfiltered list; a genre filter is recommend_for_users' alone
     result = {'recommendations': why} if filtered else recommend_from_user(model, uid, handler, seen_items)
     because = {rec['title']: rec['because'] for rec in why}
